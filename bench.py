@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- TFHE gate bootstraps/sec (STD128) on MI355X, driver contract.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--total T | --batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--total T | --batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) bench.py starts the torch.distributed.run
@@ -11,13 +11,26 @@ A step = one EvalBinGate(AND) pass over BASELINE config 4's global batch of T = 
 independent STD128 GINX gate pairs, sharded contiguously over the N ranks (strong
 scaling: T / N gates per GPU, no data-path collective), inputs resident in HBM:
 gate prep + blind rotation (k_blind_rotate_ginx), then key switch + ModSwitch
-(k_keyswitch_tiled).  Rank 0 prints ONE JSON line.  In the same line:
+(k_keyswitch_tiled).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the line: value (bootstraps/s), ms_per_step, and what follows from the HIP events of the timed
+steps themselves:
 
   * roofline       -- the dominant kernel (blind rotation): algorithmic bytes / launch
                       time (HIP events on the launch stream) vs HBM peak; tiny by
                       construction (the BSK is reused by every gate of the batch);
   * valu_roofline  -- the same kernel against the bound that binds: modular multiplies/s
-                      vs the half-rate 32-bit integer multiply issue peak;
+                      vs the half-rate 32-bit integer multiply issue peak.
+
+--dump-outputs DIR writes what the last timed step computed, as float64: DIR/out_b.npy (every gate's b)
+and DIR/out_a.npy (the a rows of a fixed, seeded sample of at most DUMP_ROWS gates, in ascending gate
+order); with N > 1 ranks each rank writes its shard as out_{a,b}_rank<r>.npy.  The inputs are seeded, so
+two builds can be compared array for array.
+
+--full adds, in the same line, whatever takes runs or checks of its own:
+
+  * verified       -- the step's outputs decrypt to AND of the input bits;
   * lmkcdey        -- BASELINE config 5: the same step on STD128_LMKCDEY (T gates,
                       same sharding), with its own roofline / valu_roofline / cpu_baseline;
   * config3        -- BASELINE config 3: B = 1024 GINX gates on one GPU (N = 1 only; warmup at least 0.2 s);
@@ -60,6 +73,7 @@ MODMUL_PER_GATE = {"ginx": 25.8e6, "lmkcdey": 24.7e6}
 K1_NAME = {"ginx": "k_blind_rotate_ginx", "lmkcdey": "k_blind_rotate_lmk"}
 PREP_NAME = {"ginx": "k_prep_ginx", "lmkcdey": "k_prep_lmk_w"}
 FULL_SHARD = 8192
+DUMP_ROWS, DUMP_SEED = 8192, 0xD0FF   # --dump-outputs: 8192 rows of 503 words are 33 MB as float64
 
 
 def log(*a):
@@ -82,6 +96,10 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every core available to this job")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-small-batch", action="store_true", help="skip the one-gate latency sub-object")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the outputs (decryption, reference hashes) and measure configs 5 and 3, one-gate "
+                         "latencies, NTT and copy rooflines and the CPU baselines (the --no-* options choose among them)")
     return ap.parse_args()
 
 
@@ -121,9 +139,24 @@ def golden_check(name, lo, hi, total, ao, bo):
     return all(_sha(ao[s - lo:s - lo + S]) + _sha(bo[s - lo:s - lo + S]) == shards[s // S] for s in range(lo, hi, S))
 
 
-def run_config(args, bf, torch, ctx, method_name, total, lo, hi, golden=None, min_warm_s=0.0):
+def dump_outputs(torch, d_ao, d_bo, out_dir, suffix=""):
+    """--dump-outputs: the output arrays of the last timed step, as a caller of the timed path receives
+    them, as float64 (every value is below 2^53): all of b, and the a rows of a fixed, seeded sample
+    of at most DUMP_ROWS gates (the same gates for the same batch size), gathered on the device."""
+    B = d_bo.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_ROWS), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    a = d_ao[torch.from_numpy(rows).to(d_ao.device)].cpu().numpy().view(np.uint64)
+    b = d_bo.cpu().numpy().view(np.uint64)
+    np.save(os.path.join(out_dir, f"out_a{suffix}.npy"), a.astype(np.float64))
+    np.save(os.path.join(out_dir, f"out_b{suffix}.npy"), b.astype(np.float64))
+
+
+def run_config(args, bf, torch, ctx, method_name, total, lo, hi, golden=None, min_warm_s=0.0, check=True, dump=None):
     """Times K steps of EvalBinGate(AND) over gates [lo, hi) of a `total`-gate batch on this
-    rank; returns the per-rank measurements (elapsed is max-reduced by the caller).  golden: the
+    rank; returns the per-rank measurements (elapsed is max-reduced by the caller).  check: copy the
+    outputs back, decrypt them and compare them with the reference hashes (else "verified", "exact" and
+    "out" are None).  dump: (directory, file name suffix) for dump_outputs() of the last step.  golden: the
     tests/golden/full_<golden>.npz reference hashes the outputs are checked against (default: the
     65,536-gate batch of the method).  min_warm_s: the warmup also lasts at least this long (config 3's
     4 ms steps: after the seconds of host-side setup the GPU clocks ramp up over its first ~25 ms,
@@ -172,16 +205,21 @@ def run_config(args, bf, torch, ctx, method_name, total, lo, hi, golden=None, mi
     elapsed = time.perf_counter() - t_start
     br_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
     ks_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))
-    ao = d_ao.cpu().numpy().view(np.uint64)
-    bo = d_bo.cpu().numpy().view(np.uint64)
-    dec = bf.decrypt(ps, method, keys.sk, ao, bo)
-    verified = bool(np.array_equal(dec, (x1[lo:hi] & x2[lo:hi]).astype(np.int64)))
-    exact = golden_check(golden or ("std128" if method_name == "ginx" else "lmkcdey"), lo, hi, total, ao, bo)
+    if dump:
+        dump_outputs(torch, d_ao, d_bo, *dump)
+    out = verified = exact = None
+    if check:
+        ao = d_ao.cpu().numpy().view(np.uint64)
+        bo = d_bo.cpu().numpy().view(np.uint64)
+        out = (ao, bo)
+        dec = bf.decrypt(ps, method, keys.sk, ao, bo)
+        verified = bool(np.array_equal(dec, (x1[lo:hi] & x2[lo:hi]).astype(np.int64)))
+        exact = golden_check(golden or ("std128" if method_name == "ginx" else "lmkcdey"), lo, hi, total, ao, bo)
     kernel = eng.gate_kernel(B)   # the blind-rotation kernel this batch launched (fhe_hip_gate_kernel)
     eng.close()
     return {"elapsed": elapsed, "br_ms": br_ms, "ks_ms": ks_ms, "verified": verified, "exact": exact, "B": B,
             "warmup_steps": n_warm,
-            "keys": keys, "inputs": (a1[lo:hi], b1[lo:hi], a2[lo:hi], b2[lo:hi]), "out": (ao, bo), "ps": ps,
+            "keys": keys, "inputs": (a1[lo:hi], b1[lo:hi], a2[lo:hi], b2[lo:hi]), "out": out, "ps": ps,
             "method": method, "kernel": kernel}
 
 
@@ -313,19 +351,21 @@ def main():
         total, scaling = args.total, "strong"
     lo, hi = shard(total, rank, world)
 
-    def measure(method_name):
-        r = run_config(args, bf, torch, ctx, method_name, total, lo, hi)
+    def measure(method_name, dump=None):
+        r = run_config(args, bf, torch, ctx, method_name, total, lo, hi, check=args.full, dump=dump)
         # launch times as well: the roofline of an N-rank line is the slowest rank's kernel
         el, bad, inexact, unknown, br, ks = max_over_ranks(
             [r["elapsed"], 0.0 if r["verified"] else 1.0, 1.0 if r["exact"] is False else 0.0,
              1.0 if r["exact"] is None else 0.0, r["br_ms"], r["ks_ms"]], device=red_dev)
         r["elapsed"], r["br_ms"], r["ks_ms"] = el, br, ks
-        r["verified"] = bad == 0.0
-        r["exact"] = None if unknown else inexact == 0.0
+        if args.full:
+            r["verified"] = bad == 0.0
+            r["exact"] = None if unknown else inexact == 0.0
         return r
 
-    main_r = measure(args.method)
-    lmk_r = measure("lmkcdey") if (args.method == "ginx" and not args.no_lmkcdey) else None
+    dump = (args.dump_outputs, f"_rank{rank}" if world > 1 else "") if args.dump_outputs else None
+    main_r = measure(args.method, dump)
+    lmk_r = measure("lmkcdey") if (args.full and args.method == "ginx" and not args.no_lmkcdey) else None
 
     result = None
     if rank == 0:
@@ -343,13 +383,13 @@ def main():
                        "paramset": "STD128" if args.method == "ginx" else "STD128_LMKCDEY",
                        "method": args.method.upper(), "global_batch": total, "batch_per_gpu": hi - lo,
                        "parallelism": f"shard{world}"},
-            "verified": main_r["verified"],
-            "bit_exact_vs_reference": main_r["exact"],
             "roofline": roofline,
             "valu_roofline": valu,
             "hbm_per_gpu": per_gpu_hbm(args.method, hi - lo, main_r["elapsed"] / args.steps),
             "distributed": topo,
         }
+        if args.full:
+            result.update(verified=main_r["verified"], bit_exact_vs_reference=main_r["exact"])
         if lmk_r is not None:
             lr, lv = rooflines("lmkcdey", lmk_r["B"], lmk_r["br_ms"], lmk_r["ks_ms"], lmk_r["kernel"])
             result["lmkcdey"] = {
@@ -361,7 +401,7 @@ def main():
                 "roofline": lr, "valu_roofline": lv, "cpu_baseline": None,
                 "hbm_per_gpu": per_gpu_hbm("lmkcdey", hi - lo, lmk_r["elapsed"] / args.steps),
             }
-    if world == 1 and not args.no_config3 and args.method == "ginx":
+    if args.full and world == 1 and not args.no_config3 and args.method == "ginx":
         c3 = run_config(args, bf, torch, ctx, "ginx", 1024, 0, 1024, golden="std128_b1024", min_warm_s=0.2)
         r3, v3 = rooflines("ginx", 1024, c3["br_ms"], c3["ks_ms"], c3["kernel"])
         alg3 = BSK_BYTES["ginx"] + KSK_BYTES["ginx"] + 1024 * (IN_BYTES_PER_GATE["ginx"] + OUT_BYTES_PER_GATE["ginx"])
@@ -376,7 +416,7 @@ def main():
             "hbm_frac_compulsory": round(alg3 / step_s / 1e9 / HBM_PEAK_GBS, 6),
             "hbm_basis": "SURVEY 8(d) config 3: BSK + KSK + 1024 x I/O = 474,677,248 B per batch / step time",
         }
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_small_batch:
             result["small_batch"] = small_batch(bf, torch, dev, stream)
         result["ntt_roofline"] = ntt_rooflines(NttPlan, torch, dev, stream, args.ntt_count)
