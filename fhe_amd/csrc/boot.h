@@ -32,6 +32,9 @@ struct BootTables {
     uint32_t w1R;    // TableI[1] (Montgomery) for the last iNTT stage
     uint32_t oneR;   // 2^32 mod Q (Montgomery 1): x -> x mod Q by one signed Montgomery product
     uint32_t nR;     // N (Montgomery): undoes the N^-1 scaling when the accumulator is written out
+    // (Table[2] +- Table[1] Table[2]) / 2 (Montgomery): the signed forward passes' first two stages as one
+    // 4-point group with two products (nt.h fwd_group_consts, bootstrap.hip fwd_group4)
+    uint32_t gpR, gmR;
 };
 
 // Digit exchange between the half-waves in the external products: ds_bpermute of the other half's

@@ -49,6 +49,26 @@
 #ifndef FHE_FWD_TIGHT
 #define FHE_FWD_TIGHT 1
 #endif
+// The signed forward passes of K1 (fwd_pass2 FM 1 / 2, fwd_pass_s) run their first two stages as one 4-point
+// group with two products instead of three (fwd_group4): one signed Montgomery product less per group, at
+// half a Q more on the group's outputs.  For FM 2 that takes the 6.67 Q above to 7.43 Q (still inside 8 Q) and
+// the LMKCDEY accumulator bound from 2.2 Q to 2.4 Q (four digits < 7.44 Q times keys < Q: 29.8 Q^2 2^-32 + Q/2
+// < 2.36 Q); make_inv_plan and make_inv_plan_ww give the same reductions for 2.4 Q as for 2.2 Q.
+// FHE_FWD_GROUP=0: ten radix-2 stages (A/B).
+#ifndef FHE_FWD_GROUP
+#define FHE_FWD_GROUP 1
+#endif
+// K1's loop inverses (GINX with Q < 2^27, the LMKCDEY / AP op-list kernel's external product and automorphism)
+// end on the digit decomposition's d + C instead of the canonical coefficient (dec_leg).  FHE_DEC_TAIL=0:
+// canonical, then decompose2 (A/B).
+#ifndef FHE_DEC_TAIL
+#define FHE_DEC_TAIL 1
+#endif
+// With FHE_DEC_TAIL, inv_pass_s also takes its last two stages together per 4-register group (two-term legs,
+// dec_leg2).  FHE_INV_GROUP=0: two radix-2 stages, then dec_leg (A/B).
+#ifndef FHE_INV_GROUP
+#define FHE_INV_GROUP 1
+#endif
 
 namespace fhe_amd {
 
@@ -62,8 +82,11 @@ struct Mod {
     uint32_t qinvp;        // Q^-1 mod 2^32 (signed Montgomery)
     int32_t nQ;            // -Q (signed Montgomery; see fresh_nq)
     uint32_t oneR;         // 2^32 mod Q: smont_mul(x, oneR) = x mod Q in (-Q, Q)
+    uint32_t gpR, gmR;     // BootTables::gpR / gmR (fwd_group4)
 };
-FHE_DEV Mod make_mod(const BootTables& T) { return Mod{T.Q, T.Q2, T.qinv, 0u - T.qinv, -(int32_t)T.Q, T.oneR}; }
+FHE_DEV Mod make_mod(const BootTables& T) {
+    return Mod{T.Q, T.Q2, T.qinv, 0u - T.qinv, -(int32_t)T.Q, T.oneR, T.gpR, T.gmR};
+}
 
 // a * bR * 2^-32 mod Q, lazily: result < Q (1 + a / 2^32 * ...) < 2Q for a < 4Q, Q < 2^28
 FHE_DEV uint32_t mont_mul(uint32_t a, uint32_t bR, const Mod& m) {
@@ -152,6 +175,27 @@ FHE_DEV void ct_bf_s(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     y                = x - t;
     x                = x + t;
 }
+// The first two signed forward stages (register bits 4 and 3: twiddles I = Table[1] everywhere, then
+// u = Table[2] below register 16 and v = Table[3] = I u above) on the group {a, b, c, d} = registers
+// {r, r|8, r|16, r|24}, r < 8.  Two radix-2 stages give
+//   a + I c +- u (b + I d)   and   a - I c +- v (b - I d),
+// and u (b + I d) = u b + (I u) d, v (b - I d) = (I u) b + u d (I^2 = -1) are a circulant in (b, d):
+// P + M and P - M with P = c+ (b + d), M = c- (b - d), c+- = (u +- I u) / 2 (Mod::gpR / gmR).  Three signed
+// Montgomery products instead of four, ten adds instead of eight; I d is never formed.
+// Inputs are balanced digits (|.| <= 2^(g-1)): b +- d cannot overflow, |I c|, |P|, |M| < Q/2 + 2^(g-4)
+// (the product bound |y| Q 2^-32 + Q/2, Q < 2^28), so every output is below 3Q/2 + 2^g -- the two radix-2
+// stages it replaces gave Q (1 + Q 2^-33) + 2^(g-1): half a Q more to carry through the later stages
+// (loosely, by "a Cooley-Tukey output is bounded by |x| + Q": |x| + 2Q here instead of |x| + Q for one stage).
+FHE_DEV void fwd_group4(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t iR, const Mod& m) {
+    const uint32_t t = smont_mul(c, iR, m);
+    const uint32_t P = smont_mul(b + d, m.gpR, m), M = smont_mul(b - d, m.gmR, m);
+    const uint32_t X = P + M, Y = P - M;
+    const uint32_t a1 = a + t, c1 = a - t;
+    a = a1 + X;
+    b = a1 - X;
+    c = c1 + Y;
+    d = c1 - Y;
+}
 // Gentleman-Sande (inverse): x, y < 2Q in, < 2Q out
 FHE_DEV void gs_bf(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     uint32_t s = csub(x + y, m.Q2);
@@ -217,18 +261,31 @@ FHE_DEV void fwd_pass(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* 
 
 // two forward NTTs at once (the digit polynomials D_h and D_{2+h}): each twiddle
 // load feeds two butterflies and every stage has 32 independent butterflies.
-// LZ (Q < 2^27): signed digits |d| <= 2^(g-1) and signed butterflies -- |v| grows by < Q per
-// stage to < 10Q + 2^(g-1) < 2^31, no reduction anywhere.  Otherwise unsigned digits < 2Q grow by
-// < 2Q per stage; < 12Q is reduced to < 6Q at the transpose (< 16Q out, Q < 2^28).
+// LZ (Q < 2^27): signed digits |d| <= 2^(g-1) and signed butterflies -- the first two stages as one group
+// (fwd_group4: < 3Q/2 + 2^g), then |v| grows by < Q per stage to < 9.5Q + 2^g < 10Q + 2^(g-1) < 2^31 (the
+// bound ten radix-2 stages had: everything downstream of the pass keeps its bounds), no reduction anywhere.
+// Otherwise unsigned digits < 2Q grow by < 2Q per stage; < 12Q is reduced to < 6Q at the transpose (< 16Q
+// out, Q < 2^28).
 // FM (forward mode): 0 unsigned lazy (above), 1 signed without reduction (Q < 2^27), 2 signed for
-// Q < 2^28: after 5 stages |v| < 5Q + 2^(g-1); the x inputs of the first B' stage (registers 0..15)
-// are reduced to (-Q, Q), so the B' outputs stay < 6Q (a Cooley-Tukey output is bounded by |x| + Q)
+// Q < 2^28: after 5 stages |v| < 4.5Q + 2^g; the x inputs of the first B' stage (registers 0..15)
+// are reduced to (-Q, Q), so the B' outputs stay < 6Q (a Cooley-Tukey output is bounded by |x| + Q).
+// FM 2 with FHE_FWD_TIGHT: no reduction; from the group's 3Q/2 + 2^g eight stages B -> (1 + 1/16) B + Q/2
+// reach 9.5 Q 1.0625^8 - 8Q + 1.63 2^g < 7.43Q + 2^(g+1) < 8Q (ten radix-2 stages: 6.67Q).
 template <int FM, bool PRE = false>
 FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int l,
                        const uint32_t* __restrict__ twA, const uint32_t* s_twB, const Mod& m) {
     constexpr bool LZ = FM != 0;
+    constexpr bool GRP = LZ && FHE_FWD_GROUP;
+    if (GRP) {
+        const uint32_t iR = twA[1];
 #pragma unroll
-    for (int b = 9; b >= 5; --b) {
+        for (int r = 0; r < 8; ++r) {
+            fwd_group4(v[r], v[r | 8], v[r | 16], v[r | 24], iR, m);
+            fwd_group4(u[r], u[r | 8], u[r | 16], u[r | 24], iR, m);
+        }
+    }
+#pragma unroll
+    for (int b = GRP ? 7 : 9; b >= 5; --b) {
         const int rb = b - 5;
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
@@ -281,8 +338,13 @@ FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int
 template <int FM>
 FHE_DEV void fwd_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* __restrict__ twA,
                         const uint32_t* s_twB, const Mod& m) {
+    if (FHE_FWD_GROUP) {
+        const uint32_t iR = twA[1];
 #pragma unroll
-    for (int b = 9; b >= 5; --b) {
+        for (int r = 0; r < 8; ++r) fwd_group4(v[r], v[r | 8], v[r | 16], v[r | 24], iR, m);
+    }
+#pragma unroll
+    for (int b = FHE_FWD_GROUP ? 7 : 9; b >= 5; --b) {
         const int rb = b - 5;
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
@@ -401,11 +463,51 @@ constexpr InvPlanS make_inv_plan() {
     return p;
 }
 
+// One leg of the last inverse stage when the result goes straight into the digit decomposition (DEC below): no
+// canonical intermediate.  a is the leg's signed word (x + y with wR = 2^32 mod Q, or x - y with wR = TableI[1]),
+// any int32 word: |a| <= 2^31 and wR <= Q - 1, so e = |a| wR 2^-32 <= (Q - 1) / 2.  With
+// s = (Q + 1) / 2, t = a wR + s 2^32 is in [2^32, Q 2^32], and the unsigned Montgomery step (t + mm Q) 2^-32,
+// mm = t (-Q^-1) mod 2^32 in [0, 2^32), lands in [s - e, s + e + Q), inside [1, 2Q): one conditional subtraction
+// gives (c + s) mod Q in [0, Q) for the leg's value c = a wR 2^-32 mod Q.  That is d + s for the centred
+// d = c or c - Q in [-(Q + 1) / 2, (Q - 1) / 2) -- the d decompose2 selects with x >= Q >> 1 -- so adding
+// cms = C - s yields decompose2's d + C in one add, without its compare and select.  Seven instructions a
+// coefficient, three of them multiplies, whatever the leg's bound; the canonical form took 2 (f + 1) + 4 on the
+// sum leg (|x + y| < 2^f Q, f = 1..4) and 9 on the difference leg.
+FHE_DEV uint32_t dec_leg(uint32_t a, uint32_t wR, uint32_t cms, const Mod& m) {
+    const uint32_t s  = m.Q - (m.Q >> 1);
+    const int64_t t   = mad_i64_i32((int32_t)a, (int32_t)wR, (int64_t)((uint64_t)s << 32));
+    const uint32_t mm = (uint32_t)t * m.qinv;
+    const uint32_t r  = (uint32_t)(((uint64_t)t + (uint64_t)mm * m.Q) >> 32);
+    return csub(r, m.Q) + cms;
+}
+// the same for a two-term leg x w1 + y w2: e = (|x| + |y|) (Q - 1) 2^-32 <= (Q - 1) / 2 needs |x| + |y| <= 2^31
+FHE_DEV uint32_t dec_leg2(uint32_t x, uint32_t w1R, uint32_t y, uint32_t w2R, uint32_t cms, const Mod& m) {
+    const uint32_t s  = m.Q - (m.Q >> 1);
+    const int64_t t   = mad_i64_i32((int32_t)x, (int32_t)w1R,
+                                    mad_i64_i32((int32_t)y, (int32_t)w2R, (int64_t)((uint64_t)s << 32)));
+    const uint32_t mm = (uint32_t)t * m.qinv;
+    const uint32_t r  = (uint32_t)(((uint64_t)t + (uint64_t)mm * m.Q) >> 32);
+    return csub(r, m.Q) + cms;
+}
+// DEC: the last two Gentleman-Sande stages (register bits 3 and 4; twiddles u = TableI[2] below register 16 and
+// v = TableI[3] = w1 u above, then w1 = TableI[1], w1^2 = -1) of the group {a, b, c, d} = registers
+// {r, r|8, r|16, r|24} without intermediates.  Two radix-2 stages give
+//   out[r] = (a + b) + (c + d),  out[r|16] = w1 ((a + b) - (c + d)),
+//   out[r|8] = u X + v Y,        out[r|24] = w1 (u X - v Y) = v X + u Y      (X = a - b, Y = c - d),
+// so the last two are two-term legs (dec_leg2) on X and Y: the products u X, v Y and w1 (..) are never formed,
+// 8 multiplies and 16 instructions for the pair instead of 12 and 22.  |a| + |b| + |c| + |d| <= 2^31 is what the
+// plan's last-stage check (sum of the two sums' bounds <= LIM) already guarantees when it placed no red3 reduction
+// on the group; a group with one takes the two stages apart as before.
+constexpr bool inv_group_ok(const InvPlanS& p, int r) {
+    return !p.red3[r] && !p.red3[r | 8] && !p.red3[r | 16] && !p.red3[r | 24];
+}
+
 // B' (EVAL, |inputs| < BIN Q / 10, signed) -> A' (COEF), canonical [0, Q) like inv_pass.
 // LZ: Q < 2^27 (sums up to 16 Q), else Q < 2^28 (8 Q; the final 2^(fin+1) Q <= 16 Q < 2^32)
-template <int BIN, bool LZ = true, bool PRE = false>
+// DEC: the outputs are decompose2's d + C (Dec::CmS passed as cms) instead: dec_digits takes them
+template <int BIN, bool LZ = true, bool PRE = false, bool DEC = false>
 FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* __restrict__ twA,
-                        const uint32_t* s_twB, uint32_t w1R, uint32_t oneR, const Mod& m) {
+                        const uint32_t* s_twB, uint32_t w1R, uint32_t oneR, const Mod& m, uint32_t cms = 0) {
     constexpr InvPlanS P = make_inv_plan<BIN, lim_s(LZ)>();
     TW_PRELOAD
 #pragma unroll
@@ -426,6 +528,7 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
     for (int r = 0; r < 32; ++r)
         if (P.redT[r]) v[r] = smont_mul(v[r], oneR, m);
     transpose32(v, tile, l);
+    constexpr bool GRP = DEC && FHE_INV_GROUP;
 #pragma unroll
     for (int b = 5; b <= 8; ++b) {
         const int rb = b - 5;
@@ -435,10 +538,24 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
             const int s = r | (1 << rb);
             if (P.red2[rb][r]) v[r] = smont_mul(v[r], oneR, m);
             if (P.red2[rb][s]) v[s] = smont_mul(v[s], oneR, m);
+            if (GRP && rb == 3 && inv_group_ok(P, r & 7)) continue;  // the group's two stages together, below
             const uint32_t w = twA[(1 << (9 - b)) + (r >> (rb + 1))];
             const uint32_t x = v[r], y = v[s];
             v[r]             = x + y;
             v[s]             = smont_mul(x - y, w, m);
+        }
+    }
+    if (GRP) {
+        const uint32_t uR = twA[2], vR = twA[3];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (!inv_group_ok(P, r)) continue;
+            const uint32_t a = v[r], b = v[r | 8], c = v[r | 16], d = v[r | 24];
+            const uint32_t s1 = a + b, s2 = c + d, X = a - b, Y = c - d;
+            v[r]      = dec_leg(s1 + s2, oneR, cms, m);
+            v[r | 16] = dec_leg(s1 - s2, w1R, cms, m);
+            v[r | 8]  = dec_leg2(X, uR, Y, vR, cms, m);
+            v[r | 24] = dec_leg2(X, vR, Y, uR, cms, m);
         }
     }
     // bit 9 (transformnat-impl.h:599-623); its N^-1 factor is already in the data.  Signed results
@@ -446,9 +563,15 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
     // (-Q, Q)) by min(d, d + Q) on the unsigned words.
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
+        if (GRP && inv_group_ok(P, r & 7)) continue;
         if (P.red3[r]) v[r] = smont_mul(v[r], oneR, m);
         if (P.red3[r | 16]) v[r | 16] = smont_mul(v[r | 16], oneR, m);
         const uint32_t x = v[r], y = v[r | 16];
+        if (DEC) {
+            v[r]      = dec_leg(x + y, oneR, cms, m);
+            v[r | 16] = dec_leg(x - y, w1R, cms, m);
+            continue;
+        }
         uint32_t s       = x + y + (m.Q << P.fin[r]);
 #pragma unroll
         for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
@@ -474,16 +597,23 @@ FHE_DEV uint32_t brv5(uint32_t x) { return __builtin_bitreverse32(x) >> 27; }
 // input bound).  Needs C + Q < 2^32 (g <= 10 with Q < 2^28; checked by Engine::gate_args).
 // SG: the digits themselves, signed (field f -> f - 2^(g-1) is the sign-extension of f with its
 // top bit flipped, so one XOR with M and a signed bit-field extract per digit).
+// CmS = C - (Q + 1) / 2: what dec_leg adds to (x + (Q + 1) / 2) mod Q to reach d + C.
 struct Dec {
-    uint32_t Q, Qh, C, CmQ, g, off, M;
+    uint32_t Q, Qh, C, CmQ, g, off, M, CmS;
 };
 FHE_DEV Dec make_dec(uint32_t Q, uint32_t g) {
     const uint32_t h = 1u << (g - 1), C = h * (1u + (1u << g) + (1u << (2 * g)));
-    return Dec{Q, Q >> 1, C, C - Q, g, Q - h, (h << g) | (h << (2 * g))};
+    return Dec{Q, Q >> 1, C, C - Q, g, Q - h, (h << g) | (h << (2 * g)), C - (Q - (Q >> 1))};
 }
+// the two retained digits from u = d + C
+template <bool SG>
+FHE_DEV void dec_digits(uint32_t u, const Dec& c, uint32_t& dA, uint32_t& dB);
 template <bool SG>
 FHE_DEV void decompose2(uint32_t x, const Dec& c, uint32_t& dA, uint32_t& dB) {
-    const uint32_t u = x >= c.Qh ? x + c.CmQ : x + c.C;  // d + C, d = x or x - Q
+    dec_digits<SG>(x >= c.Qh ? x + c.CmQ : x + c.C, c, dA, dB);  // d + C, d = x or x - Q
+}
+template <bool SG>
+FHE_DEV void dec_digits(uint32_t u, const Dec& c, uint32_t& dA, uint32_t& dB) {
     if (SG) {
         const int32_t w = (int32_t)(u ^ c.M);
         dA              = (uint32_t)__builtin_amdgcn_sbfe(w, c.g, c.g);
@@ -656,12 +786,16 @@ __global__ void __launch_bounds__(256, FHE_WAVES_PER_EU)
         // --- iNTT of a copy of acc -> canonical COEF (AddToAccCGGI :104-106)
 #pragma unroll
         for (int r = 0; r < 32; ++r) dA[r] = acc[r];
-        if (LZ) inv_pass_s<kAccBoundLZ, true, true>(dA, tile, l, twAi, s_twBi, T.w1R, T.oneR, m);
+        constexpr bool TAIL = LZ && FHE_DEC_TAIL;  // the inverse pass ends on d + C (dec_leg), not on [0, Q)
+        if (LZ) inv_pass_s<kAccBoundLZ, true, true, TAIL>(dA, tile, l, twAi, s_twBi, T.w1R, T.oneR, m, dec.CmS);
         else inv_pass(dA, tile, l, T.twA_inv, s_twBi, T.w1R, m);
         // --- SignedDigitDecompose (rgsw-acc.cpp:54-91): drop the lowest signed digit,
         //     keep the next two.  Half h decomposes acc_h: dA = D_h, dB = D_{2+h}.
 #pragma unroll
-        for (int r = 0; r < 32; ++r) decompose2<LZ>(dA[r], dec, dA[r], dB[r]);
+        for (int r = 0; r < 32; ++r) {
+            if (TAIL) dec_digits<LZ>(dA[r], dec, dA[r], dB[r]);
+            else decompose2<LZ>(dA[r], dec, dA[r], dB[r]);
+        }
         // --- NTT of the four digit polynomials (two per pass, one per half)
         fwd_pass2<LZ ? 1 : 0, true>(dA, dB, tile, l, twAf, s_twBf, m);
         // --- external product + CMUX, slot by slot.  Lane (h, l) owns slots
@@ -923,9 +1057,10 @@ constexpr InvPlanWW make_inv_plan_ww() {
 }
 // EVAL (layout C, |v| < BIN Q / 10) -> canonical COEF (layout A); the keys carry N^-1, so the last
 // stage scales by TableI[1] only (as inv_pass_s).  tile: 1088 words of this wave; s_tabI: TableI.
-template <int BIN, bool LZ>
+// DEC: decompose2's d + C instead of the canonical coefficient, as inv_pass_s (the LMKCDEY automorphism)
+template <int BIN, bool LZ, bool DEC = false>
 FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t* s_tabI, uint32_t w1R,
-                        uint32_t oneR, const Mod& m) {
+                        uint32_t oneR, const Mod& m, uint32_t cms = 0) {
     constexpr InvPlanWW P = make_inv_plan_ww<BIN, lim_s(LZ)>();
     auto redp = [&](int st) {
 #pragma unroll
@@ -999,6 +1134,11 @@ FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const uint32_t x = v[r], y = v[r | 8];
+        if (DEC) {
+            v[r]     = dec_leg(x + y, oneR, cms, m);
+            v[r | 8] = dec_leg(x - y, w1R, cms, m);
+            continue;
+        }
         uint32_t s       = x + y + (m.Q << P.fin[r]);
 #pragma unroll
         for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
@@ -1038,8 +1178,23 @@ FHE_DEV void automorphism_wide(uint32_t (&v)[32], uint32_t (&a0)[16], uint32_t* 
 
 }  // namespace
 
-// |acc| between ops (units of Q/10): 2 Q, or 2.2 Q for Q >= 2^27 with FHE_FWD_TIGHT (see there)
-template <bool LZ> constexpr int kLmkAcc = (!LZ && FHE_FWD_TIGHT) ? 22 : 20;
+// |acc| between ops (units of Q/10): 2 Q, or for Q >= 2^27 with FHE_FWD_TIGHT 2.2 Q, 2.4 Q with the grouped
+// first stages (FHE_FWD_GROUP, see there)
+template <bool LZ> constexpr int kLmkAcc = (!LZ && FHE_FWD_TIGHT) ? (FHE_FWD_GROUP ? 24 : 22) : 20;
+// the larger bound is free: the inverse plans reduce no more often from 2.4 Q than from 2.2 Q
+constexpr int inv_plan_reds(const InvPlanS& p) {
+    int n = 0;
+    for (int r = 0; r < 32; ++r) {
+        for (int b = 0; b < 5; ++b) n += p.red1[b][r];
+        for (int b = 0; b < 4; ++b) n += p.red2[b][r];
+        n += p.redT[r] + p.red3[r];
+    }
+    for (int r = 0; r < 16; ++r) n += p.fin[r];
+    return n;
+}
+static_assert(inv_plan_reds(make_inv_plan<24, lim_s(false)>()) == inv_plan_reds(make_inv_plan<22, lim_s(false)>()) &&
+                  make_inv_plan_ww<24, lim_s(false)>().cost == make_inv_plan_ww<22, lim_s(false)>().cost,
+              "kLmkAcc 24 must cost the inverse transforms nothing over 22");
 // DM: the AP/DM accumulator runs the same op loop with external products only (AddToAccDM ==
 // AddToAccLMKCDEY, rgsw-acc-dm.cpp:119-145) and no initial automorphism of acc1.
 // DM needs no automorphism path and fits 168 VGPRs: 3 waves per SIMD
@@ -1133,9 +1288,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
             uint4 kq[KPF + 1][4];
 #pragma unroll
             for (int r = 0; r < 32; ++r) dA[r] = acc[r];
-            inv_pass_s<kLmkAcc<LZ>, LZ, !DM && FHE_LMK_PRE>(dA, tile, l, twAi, s_twBi, T.w1R, m.oneR, m);
+            inv_pass_s<kLmkAcc<LZ>, LZ, !DM && FHE_LMK_PRE, FHE_DEC_TAIL>(dA, tile, l, twAi, s_twBi, T.w1R, m.oneR, m,
+                                                                          dec.CmS);
 #pragma unroll
-            for (int r = 0; r < 32; ++r) decompose2<true>(dA[r], dec, dA[r], dB[r]);
+            for (int r = 0; r < 32; ++r) {
+                if (FHE_DEC_TAIL) dec_digits<true>(dA[r], dec, dA[r], dB[r]);
+                else decompose2<true>(dA[r], dec, dA[r], dB[r]);
+            }
             fwd_pass2<FM, !DM && FHE_LMK_PRE>(dA, dB, tile, l, twAf, s_twBf, m);
             // one 16-byte vector per digit row and 4 slots (boot.h row_off)
 #pragma unroll
@@ -1169,8 +1328,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
                     const uint32_t D0 = dA[r], D2 = dB[r];
                     const uint32_t D1 = (FHE_LMK_ABL & 8) ? dA[r] ^ 1u : PIPE ? xq[kk & 1][2 * e] : other_half(dA[r], xaddr);
                     const uint32_t D3 = (FHE_LMK_ABL & 8) ? dB[r] ^ 1u : PIPE ? xq[kk & 1][2 * e + 1] : other_half(dB[r], xaddr);
-                    // |D| < 10Q + 2^8 (Q < 2^27) or 6Q (Q < 2^28; 6.67Q with FHE_FWD_TIGHT): |S| < 40 Q^2
-                    // or 24 Q^2 (26.7 Q^2), so |S| 2^-32 + Q/2 < 2Q (2.2Q: kLmkAcc)
+                    // |D| < 10Q + 2^8 (Q < 2^27) or 6Q (Q < 2^28; with FHE_FWD_TIGHT 6.67Q, 7.44Q with the grouped
+                    // first stages): |S| < 40 Q^2 or 24 Q^2 (26.7 Q^2, 29.8 Q^2), so |S| 2^-32 + Q/2 < 2Q
+                    // (2.2Q, 2.4Q: kLmkAcc)
                     const int64_t S = (int64_t)mac4<true>(D0, D1, D2, D3, KC(0), KC(1), KC(2), KC(3), 0);
                     acc[r] = smont_red(S, m);
 #undef KC
@@ -1190,7 +1350,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
                 // digits scattered into the two tiles in A' order (digit A for half 0, B for half 1)
                 uint32_t a0[16];
                 automorphism_wide(acc, a0, tile, tileW, l, lane, kexp);
-                inv_wave_s<kLmkAcc<LZ>, LZ>(a0, tileW, lane, s_tabI, T.w1R, m.oneR, m);
+                inv_wave_s<kLmkAcc<LZ>, LZ, FHE_DEC_TAIL>(a0, tileW, lane, s_tabI, T.w1R, m.oneR, m, dec.CmS);
 #if FHE_LMK_SWAP
                 // coefficient x = (r << 6) | lane goes to half-wave register (x >> 5), lane x & 31 of half 0
                 // (digit A) and half 1 (digit B): one half exchange per register pair (v_permlane32_swap:
@@ -1198,7 +1358,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     uint32_t x, y;
-                    decompose2<true>(a0[r], dec, x, y);
+                    if (FHE_DEC_TAIL) dec_digits<true>(a0[r], dec, x, y);
+                    else decompose2<true>(a0[r], dec, x, y);
                     const auto p = __builtin_amdgcn_permlane32_swap(x, y, false, false);
                     dA[2 * r]     = p[0];
                     dA[2 * r + 1] = p[1];
@@ -1207,7 +1368,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     uint32_t x, y;
-                    decompose2<true>(a0[r], dec, x, y);
+                    if (FHE_DEC_TAIL) dec_digits<true>(a0[r], dec, x, y);
+                    else decompose2<true>(a0[r], dec, x, y);
                     const uint32_t c = ((uint32_t)r << 6) | (uint32_t)lane;
                     tileW[(c & 31) * 33 + (c >> 5)]         = x;
                     tileW[kTile + (c & 31) * 33 + (c >> 5)] = y;
@@ -1248,7 +1410,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
                     const uint32_t P0 = dA[r], P1 = xa[kk & 1][e];
                     const uint32_t c0 = e == 0 ? k0.x : e == 1 ? k0.y : e == 2 ? k0.z : k0.w;
                     const uint32_t c1 = e == 0 ? k1.x : e == 1 ? k1.y : e == 2 ? k1.z : k1.w;
-                    // |S| < 2 (6Q) Q + 2Q Q -> |acc| < 14 Q^2 2^-32 + Q/2 < 2Q
+                    // |S| < 2 (7.44Q) Q + 2.4Q Q -> |acc| < 17.3 Q^2 2^-32 + Q/2 < 2Q
                     int64_t S = (int64_t)(int32_t)P0 * (int32_t)c0 + (int64_t)(int32_t)P1 * (int32_t)c1;
                     S += (int64_t)(int32_t)acc[r] * (int32_t)oneRh;
                     acc[r] = smont_red(S, m);

@@ -16,6 +16,7 @@
 #include "multi.h"
 #include "keygen.h"
 #include "ntt.h"
+#include "nt.h"
 #include "boot.h"
 
 using namespace fhe_amd;
@@ -798,6 +799,13 @@ int fhe_hip_device_memory(int device, size_t* free_bytes, size_t* total_bytes) {
     if (e != hipSuccess) return hip_fail(e, "hipMemGetInfo");
     if (free_bytes) *free_bytes = fr;
     if (total_bytes) *total_bytes = tot;
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_fwd_group_consts(uint64_t Q, uint64_t t1, uint64_t t2, uint64_t t3, uint64_t* c_plus, uint64_t* c_minus) {
+    if (!c_plus || !c_minus) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (!fwd_group_consts(Q, t1, t2, t3, c_plus, c_minus))
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "Table[3] != Table[1] * Table[2] (or Table[1]^2 != -1) mod Q");
     return FHE_HIP_OK;
 }
 

@@ -452,6 +452,14 @@ void Engine::build_tables() {
         twAf[i] = to_mont(h.tab[i], Q);
         twAi[i] = to_mont(h.tabI[i], Q);
     }
+    // the signed forward passes read Table[1..3] only through these two constants: no table without them
+    uint64_t gp = 0, gm = 0;
+    if (!fwd_group_consts(Q, h.tab[1], h.tab[2], h.tab[3], &gp, &gm))
+        throw std::invalid_argument("build_tables: Table[3] != Table[1] * Table[2] (or Table[1]^2 != -1) mod Q");
+    // the signed inverse pass's last 4-register group (bootstrap.hip dec_leg2) relies on the same relation in TableI
+    uint64_t ip = 0, im = 0;
+    if (!fwd_group_consts(Q, h.tabI[1], h.tabI[2], h.tabI[3], &ip, &im))
+        throw std::invalid_argument("build_tables: TableI[3] != TableI[1] * TableI[2] (or TableI[1]^2 != -1) mod Q");
     // lane-major tables of the stages on bits 4..0 (bootstrap.hip, twb_off)
     for (int b = 4; b >= 0; --b) {
         const int per = 1 << (4 - b), off = 32 * (per - 1);
@@ -502,6 +510,8 @@ void Engine::build_tables() {
     tabs_.w1R = to_mont(h.tabI[1], Q);
     tabs_.oneR = to_mont(1, Q);
     tabs_.nR = to_mont(p_.N, Q);
+    tabs_.gpR = to_mont(gp, Q);
+    tabs_.gmR = to_mont(gm, Q);
 }
 
 // logGen of rgsw-cryptoparameters.cpp:115-127 (k_prep_lmk_w's group positions)

@@ -27,6 +27,22 @@ inline uint32_t ilog2(uint64_t x) { uint32_t r = 0; while (x > 1) { x >>= 1; ++r
 inline uint32_t shoup32(uint64_t w, uint64_t Q) { return (uint32_t)(((u128)w << 32) / Q); }
 inline uint64_t shoup64(uint64_t w, uint64_t Q) { return (uint64_t)(((u128)w << 64) / Q); }
 
+// Constants of the signed forward passes' first 4-point group (bootstrap.hip fwd_group4): with I = Table[1],
+// u = Table[2], v = Table[3] (plain residues mod an odd prime Q), the two stage-2 products of a group are
+// u x + (I u) y and (I u) x + u y, a circulant, so they equal P + M and P - M with P = c+ (x + y),
+// M = c- (x - y), c+- = (u +- I u) / 2.  That needs I^2 = -1 and v = +I u (what the bit-reversed power table
+// gives: Table[3] = psi^(3N/4) = psi^(N/2) psi^(N/4)); v = -I u would swap the group's last two outputs, which
+// the kernels do not implement.  False (and no constants) for any other table.
+inline bool fwd_group_consts(uint64_t Q, uint64_t I, uint64_t u, uint64_t v, uint64_t* cp, uint64_t* cm) {
+    if (Q < 3 || !(Q & 1) || I >= Q || u >= Q || v >= Q) return false;
+    const uint64_t Iu = mulmod(I, u, Q);
+    if (mulmod(I, I, Q) != Q - 1 || v != Iu) return false;
+    const uint64_t half = (Q + 1) / 2;  // 2^-1 mod Q
+    *cp = mulmod(addmod(u, Iu, Q), half, Q);
+    *cm = mulmod(submod(u, Iu, Q), half, Q);
+    return true;
+}
+
 // Host NTT (same transform as the device kernels) for key generation.
 struct HostNtt {
     uint32_t N = 0, logN = 0;

@@ -393,6 +393,11 @@ int fhe_hip_synchronize(int device);
 int fhe_hip_device_count(int* count);
 /* Backend::DeviceMemory (backend.h:87): free / total bytes of the device (either may be NULL) */
 int fhe_hip_device_memory(int device, size_t* free_bytes, size_t* total_bytes);
+/* Table check of the fused accumulator kernels' signed forward transform (host only, no device): with
+ * t1, t2, t3 = Table[1..3] of the negacyclic NTT mod the odd prime Q (plain residues), the constants
+ * c+- = (t2 +- t1 t2) / 2 mod Q of its first 4-point group.  FHE_HIP_ERR_INVALID_PARAM unless t1^2 = -1 and
+ * t3 = t1 t2 mod Q -- the check the context's table builder makes before any kernel can run. */
+int fhe_hip_fwd_group_consts(uint64_t Q, uint64_t t1, uint64_t t2, uint64_t t3, uint64_t* c_plus, uint64_t* c_minus);
 /* message of the last error on this host thread */
 const char* fhe_hip_last_error(void);
 
