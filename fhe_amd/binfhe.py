@@ -147,6 +147,25 @@ def _setup(L):
     L.fhe_hip_encrypt_large.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, sz, u64, ctypes.c_uint32, vp, vp]
     L.fhe_hip_gate_kernel.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_char_p)]
     L.fhe_hip_copy_keys.argtypes = [vp, vp]
+    u32, pu32, psz = ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)
+    L.fhe_hip_circuit_create.argtypes = [ctypes.POINTER(vp)]
+    L.fhe_hip_circuit_destroy.argtypes = [vp]
+    L.fhe_hip_circuit_destroy.restype = None
+    L.fhe_hip_circuit_add_input.argtypes = [vp, pu32]
+    L.fhe_hip_circuit_add_not.argtypes = [vp, u32, pu32]
+    L.fhe_hip_circuit_add_gate.argtypes = [vp, ctypes.c_int, u32, u32, pu32]
+    L.fhe_hip_circuit_add_cmux.argtypes = [vp, u32, u32, u32, pu32]
+    L.fhe_hip_circuit_add_bootstrap.argtypes = [vp, u32, pu32]
+    L.fhe_hip_circuit_mark_output.argtypes = [vp, u32]
+    L.fhe_hip_circuit_finalize.argtypes = [vp]
+    L.fhe_hip_circuit_set_max_slots.argtypes = [vp, sz]
+    L.fhe_hip_circuit_counts.argtypes = [vp, psz, psz, psz, psz]
+    L.fhe_hip_circuit_level.argtypes = [vp, sz, psz, psz]
+    L.fhe_hip_circuit_node_row.argtypes = [vp, u32, pu32, pu32]
+    L.fhe_hip_eval_circuit_batch.argtypes = [vp, vp, sz, u32, vp, vp, u32, vp, vp]
+    L.fhe_hip_eval_circuit_batch_device.argtypes = [vp, vp, sz, u32, vp, vp, u32, vp, vp, vp]
+    L.fhe_hip_gate_fold.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, pu32,
+                                    ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L._binfhe_ready = True
     return L
 
@@ -388,8 +407,128 @@ def cereal_write_context(paramset, method):
     return out.tobytes()
 
 
+def gate_fold(paramset, method, gate, ref_gate=AND):
+    """(q1(gate), doubled, bshift) of fhe_hip_gate_fold: `gate`'s test vector at b is ref_gate's at b + bshift"""
+    dbl, bshift, q1 = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(L().fhe_hip_gate_fold(paramset, method, gate, ref_gate, ctypes.byref(dbl), ctypes.byref(bshift),
+                                ctypes.byref(q1)))
+    return q1.value, bool(dbl.value), bshift.value
+
+
+class Circuit:
+    """A boolean circuit (fhe_hip_circuit): a DAG of inputs, 2-input gates, NOT, CMUX and BOOTSTRAP nodes built on
+    the host, evaluated level by level on the GPU by GateEngine.eval_circuit.  Node ids are consecutive from 0.
+
+        c = Circuit()
+        x, y = c.input(), c.input()
+        c.output(c.gate(XOR, x, c.not_(y)))
+        ao, bo = engine.eval_circuit(c, a_in, b_in)      # a_in [n_in][B][n] -> ao [n_out][B][n]
+    """
+
+    def __init__(self):
+        self._h = vp()
+        check(L().fhe_hip_circuit_create(ctypes.byref(self._h)))
+        self.finalized = False
+
+    def close(self):
+        if self._h:
+            L().fhe_hip_circuit_destroy(self._h)
+            self._h = vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _add(self, fn, *args):
+        i = ctypes.c_uint32()
+        check(fn(self._h, *args, ctypes.byref(i)))
+        return i.value
+
+    def input(self):
+        return self._add(L().fhe_hip_circuit_add_input)
+
+    def not_(self, x):
+        """EvalNOT: no bootstrap, folded into the nodes that use it"""
+        return self._add(L().fhe_hip_circuit_add_not, x)
+
+    def gate(self, g, x, y):
+        return self._add(L().fhe_hip_circuit_add_gate, g, x, y)
+
+    def cmux(self, c0, c1, sel):
+        """sel ? c1 : c0 (GateEngine.eval_cmux(c0, c1, sel))"""
+        return self._add(L().fhe_hip_circuit_add_cmux, c0, c1, sel)
+
+    def bootstrap(self, x):
+        return self._add(L().fhe_hip_circuit_add_bootstrap, x)
+
+    def output(self, x):
+        check(L().fhe_hip_circuit_mark_output(self._h, x))
+        return x
+
+    def finalize(self):
+        check(L().fhe_hip_circuit_finalize(self._h))
+        self.finalized = True
+        return self
+
+    def set_max_slots(self, m):
+        check(L().fhe_hip_circuit_set_max_slots(self._h, m))
+
+    def _counts(self, plan):
+        v = [ctypes.c_size_t() for _ in range(4)]
+        refs = [ctypes.byref(x) for x in v]
+        check(L().fhe_hip_circuit_counts(self._h, refs[0], refs[1], *(refs[2:] if plan else (None, None))))
+        return [x.value for x in v]
+
+    @property
+    def num_inputs(self):
+        return self._counts(False)[0]
+
+    @property
+    def num_outputs(self):
+        return self._counts(False)[1]
+
+    @property
+    def num_levels(self):
+        return self._counts(True)[2]
+
+    @property
+    def num_bootstraps(self):
+        return self._counts(True)[3]
+
+    def level(self, i):
+        """(width, first pool row) of level i (0: the inputs)"""
+        w, r = ctypes.c_size_t(), ctypes.c_size_t()
+        check(L().fhe_hip_circuit_level(self._h, i, ctypes.byref(w), ctypes.byref(r)))
+        return w.value, r.value
+
+    def node_row(self, x):
+        """(pool row, negated) node x resolves to"""
+        r, ng = ctypes.c_uint32(), ctypes.c_uint32()
+        check(L().fhe_hip_circuit_node_row(self._h, x, ctypes.byref(r), ctypes.byref(ng)))
+        return r.value, bool(ng.value)
+
+
 class GateEngine:
     """One MI355X context (fhe_hip_ctx): resident keys + batched gate bootstrapping."""
+
+    def eval_circuit(self, circ, a_in, b_in):
+        """B instances of a finalized Circuit: a_in [n_in][B][n], b_in [n_in][B] -> ([n_out][B][n], [n_out][B])"""
+        a_in, b_in = _u64(a_in), _u64(b_in)
+        n_in = b_in.shape[0] if b_in.ndim == 2 else 0
+        B = b_in.shape[1] if b_in.ndim == 2 else 0
+        n_out = circ.num_outputs
+        ao = np.zeros((n_out, B, self.params.n), np.uint64)
+        bo = np.zeros((n_out, B), np.uint64)
+        check(L().fhe_hip_eval_circuit_batch(self._h, circ._h, B, n_in, ptr(a_in), ptr(b_in), n_out, ptr(ao), ptr(bo)))
+        return ao, bo
+
+    def eval_circuit_device(self, circ, count, d_a_in, d_b_in, d_ao, d_bo, stream=None):
+        """the same on device buffers, asynchronous on stream (fhe_hip_eval_circuit_batch_device)"""
+        check(L().fhe_hip_eval_circuit_batch_device(self._h, circ._h, count, circ.num_inputs, vp(d_a_in), vp(d_b_in),
+                                                    circ.num_outputs, vp(d_ao), vp(d_bo),
+                                                    vp(stream) if stream else None))
 
     def __init__(self, paramset, method, device=0, _handle=None):
         self._h = vp()
@@ -965,3 +1104,72 @@ class BinFHEContext:
         b2 = np.array([c.b for c in ct2], np.uint64)
         ao, bo = self.engine.eval_gate(gate, a1, b1, a2, b2)
         return [LWECiphertext(ao[i], int(bo[i]), self.params.q) for i in range(len(bo))]
+
+
+class BatchDAG:
+    """BatchDAG (src/binfhe/include/batch/binfhe-batch.h:229-279) over Circuit: the reference's Execute runs the
+    operations one by one (batch.cpp:429-482); this one runs the DAG level by level on the GPU.  Ids number the
+    ciphertexts in the order they are added, as the reference's do."""
+
+    def __init__(self, cc):
+        self.cc = cc
+        self.Clear()
+
+    def Clear(self):
+        self._circ = Circuit()
+        self._inputs = []       # LWECiphertext per circuit input
+        self._results = None
+        self._count = 0
+
+    def _new(self, node):
+        assert node == self._count
+        self._count += 1
+        self._results = None
+        return node
+
+    def AddCiphertext(self, ct):
+        if ct.modulus != self.cc.params.q or len(ct.a) != self.cc.params.n:
+            raise FheHipError(-2, "BatchDAG: ciphertexts mod q of dimension n only")
+        i = self._new(self._circ.input())
+        self._inputs.append(ct)
+        return i
+
+    def AddBootstrap(self, input_id):
+        return self._new(self._circ.bootstrap(input_id))
+
+    def AddEvalFunc(self, input_id, lut):
+        raise NotImplementedError("BatchDAG.AddEvalFunc is not built: circuits hold gates, NOT, CMUX and Bootstrap "
+                                  "nodes only (use BinFHEContext.EvalFunc)")
+
+    def AddBinGate(self, gate, input1_id, input2_id):
+        return self._new(self._circ.gate(gate, input1_id, input2_id))
+
+    def AddCMUX(self, sel_id, true_id, false_id):
+        """EvalCMUXBatch(sel, true, false) (batch.cpp:212-249): EvalBinGate(CMUX, {sel, true, false}), which the
+        reference evaluates as false ? true : sel -- as BinFHEContext.EvalCMUXBatch here does"""
+        return self._new(self._circ.cmux(sel_id, true_id, false_id))
+
+    def Execute(self, flags=0):
+        """every added node is an output; True on success"""
+        if self._circ.finalized:      # executed before: the same DAG again
+            circ = self._circ
+        else:
+            for i in range(self._count):
+                self._circ.output(i)
+            circ = self._circ.finalize()
+        if self._count == 0:
+            self._results = []
+            return True
+        n = self.cc.params.n
+        a = np.stack([c.a for c in self._inputs]).reshape(-1, 1, n) if self._inputs else np.zeros((0, 1, n), np.uint64)
+        b = np.array([c.b for c in self._inputs], np.uint64).reshape(-1, 1)
+        ao, bo = self.cc.engine.eval_circuit(circ, a, b)
+        self._results = [LWECiphertext(ao[i, 0], int(bo[i, 0]), self.cc.params.q) for i in range(self._count)]
+        return True
+
+    def GetResult(self, id):
+        if id >= self._count:
+            raise IndexError("Invalid ciphertext ID")
+        if self._results is None:
+            raise FheHipError(-11, "BatchDAG: Execute first")
+        return self._results[id]

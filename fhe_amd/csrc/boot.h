@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "circuit.h"
+
 namespace fhe_amd {
 
 // Twiddle/monomial tables for the fused accumulator kernels (all u32,
@@ -105,6 +107,28 @@ struct GateInputs {
 
 // GINX/CGGI: inputs -> monomial exponents + test-vector b
 hipError_t launch_prep_ginx(const GateArgs& g, const GateInputs& in, uint16_t* idx, uint32_t* tvb, hipStream_t s);
+
+// One level of a circuit (circuit.h) as prep input: B instances of `nodes` gates of any 2-input types (and
+// BOOTSTRAP nodes), operands read by row from the ciphertext pool pool_a [rows][n] / pool_b [rows] (u64, mod q).
+// Slot s of the level is node s / B, instance s % B, its operands the rows src B + instance of desc[node];
+// a launch covers slots [first, first + g.count).  The launch's GateArgs are AND's: every node's window is
+// moved onto it by its bshift (DESIGN.md §4 "Circuits").
+struct CircuitLevel {
+    const uint64_t* pool_a;
+    const uint64_t* pool_b;
+    const CircuitSlot* desc;  // device array, the level's nodes
+    uint32_t nodes, B, first;
+};
+// the three preps on a circuit level: the same kernel bodies as launch_prep_ginx / _lmk / _dm over PoolFetch
+hipError_t launch_prep_ginx_pool(const GateArgs& g, const CircuitLevel& lv, uint16_t* idx, uint32_t* tvb, hipStream_t s);
+hipError_t launch_prep_lmk_pool(const GateArgs& g, const CircuitLevel& lv, const int16_t* logGen, uint16_t* ops,
+                                uint32_t* nops, uint32_t* tvb, uint32_t maxops, uint32_t numAutoKeys, hipStream_t s);
+hipError_t launch_prep_dm_pool(const GateArgs& g, const CircuitLevel& lv, uint16_t* ops, uint32_t* nops, uint32_t* tvb,
+                               uint32_t maxops, uint32_t baseR, uint32_t digitsR, hipStream_t s);
+// circuit outputs (circuit_gather.hip): pool rows outs[o].src B + i into a_out [n_out][B][n] / b_out [n_out][B],
+// EvalNOT (binfhe-base-scheme.cpp:223-236: (-a, q/4 - b) mod q) applied where outs[o].neg
+hipError_t launch_circuit_gather(const uint64_t* pool_a, const uint64_t* pool_b, const CircuitOut* outs, uint32_t n_out,
+                                 uint32_t B, uint32_t n, uint32_t q, uint64_t* a_out, uint64_t* b_out, hipStream_t s);
 // GINX with two waves per gate (one RLWE component each): keys repacked from the resident GINX
 // layout (launch_repack_ginx2); launched for gate batches with Q < 2^27 and ciphertext modulus q < 2N
 hipError_t launch_repack_ginx2(const void* bsk, uint32_t n, void* bsk2, hipStream_t s);

@@ -673,17 +673,57 @@ FHE_DEV uint32_t combine(const GateInputs& in, const uint64_t* const* v, size_t 
     s &= qm;
     return dbl ? (2 * s) & qm : s;
 }
+
+// Where a prep kernel's ciphertexts come from.  a(t, n, qm): word t = gate * n + i of the combined a;
+// b(gate, qm): the combined b.
+// ColumnFetch: GateInputs' contiguous columns, one gate type per launch (every entry point but the circuits').
+struct ColumnFetch {
+    GateInputs in;
+    uint32_t dbl;
+    FHE_DEV uint32_t a(size_t t, uint32_t, uint32_t qm) const { return combine(in, in.a, t, 0, qm, dbl); }
+    FHE_DEV uint32_t b(uint32_t gate, uint32_t qm) const { return combine(in, in.b, gate, in.boff, qm, dbl); }
+};
+// PoolFetch: a circuit level (circuit.h).  Slot s = first + gate of the level is node s / B, instance s % B;
+// its operands are the pool rows src B + instance, combined per the node's CircuitSlot.  bshift moves the
+// node's gate window onto the launch's (AND's): added to b after the doubling, never to a.
+struct PoolFetch {
+    const uint64_t* pa;       // [rows][n]
+    const uint64_t* pb;       // [rows]
+    const CircuitSlot* desc;  // the level's nodes
+    uint32_t B, first;
+    FHE_DEV uint32_t sum(const CircuitSlot& d, uint32_t x0, uint32_t x1, uint32_t boff, uint32_t qm) const {
+        uint32_t s = boff + ((d.flags & CircuitSlot::kNeg0) ? 0u - x0 : x0);
+        if (!(d.flags & CircuitSlot::kOne)) s += (d.flags & CircuitSlot::kNeg1) ? 0u - x1 : x1;
+        s &= qm;
+        return (d.flags & CircuitSlot::kDbl) ? (2 * s) & qm : s;
+    }
+    FHE_DEV uint32_t a(size_t t, uint32_t n, uint32_t qm) const {
+        const uint32_t gate = (uint32_t)(t / n), i = (uint32_t)(t - (size_t)gate * n);
+        const uint32_t s = first + gate, node = s / B, inst = s - node * B;
+        const CircuitSlot d = desc[node];
+        return sum(d, (uint32_t)pa[((size_t)d.src0 * B + inst) * n + i], (uint32_t)pa[((size_t)d.src1 * B + inst) * n + i],
+                   0, qm);
+    }
+    FHE_DEV uint32_t b(uint32_t gate, uint32_t qm) const {
+        const uint32_t s = first + gate, node = s / B, inst = s - node * B;
+        const CircuitSlot d = desc[node];
+        const uint32_t v = sum(d, (uint32_t)pb[(size_t)d.src0 * B + inst], (uint32_t)pb[(size_t)d.src1 * B + inst],
+                               d.boff_pre, qm);
+        return (v + d.bshift) & qm;
+    }
+};
 }  // namespace
 
-__global__ void k_prep_ginx(GateInputs in, GateArgs g, uint16_t* __restrict__ idx, uint32_t* __restrict__ tvb) {
+template <class F>
+__global__ void k_prep_ginx(F in, GateArgs g, uint16_t* __restrict__ idx, uint32_t* __restrict__ tvb) {
     const uint64_t total = (uint64_t)g.count * g.n;
     const uint32_t qm = g.ctmod - 1, mbymod = 2 * g.N / g.ctmod;
     for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t a = combine(in, in.a, t, 0, qm, g.xor_double);
+        const uint32_t a = in.a(t, g.n, qm);
         idx[t] = (uint16_t)(((g.ctmod - a) & qm) * mbymod);
     }
     for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < g.count; t += (uint64_t)gridDim.x * blockDim.x)
-        tvb[t] = combine(in, in.b, t, in.boff, qm, g.xor_double);
+        tvb[t] = in.b((uint32_t)t, qm);
 }
 
 // ---------------------------------------------------------------------------
@@ -923,7 +963,26 @@ hipError_t launch_prep_ginx(const GateArgs& g, const GateInputs& in, uint16_t* i
     if (in.k < 1 || in.k > 4) return hipErrorInvalidValue;
     const uint64_t total = (uint64_t)g.count * g.n;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_prep_ginx, dim3(blocks), dim3(256), 0, s, in, g, idx, tvb);
+    hipLaunchKernelGGL(k_prep_ginx<ColumnFetch>, dim3(blocks), dim3(256), 0, s, ColumnFetch{in, g.xor_double}, g, idx,
+                       tvb);
+    return hipGetLastError();
+}
+
+namespace {
+// a level chunk's slots must lie inside the level: first + count <= nodes * B, in 32 bits
+bool pool_args_ok(const GateArgs& g, const CircuitLevel& lv) {
+    return lv.pool_a && lv.pool_b && lv.desc && lv.B && (uint64_t)lv.first + g.count <= (uint64_t)lv.nodes * lv.B &&
+           (uint64_t)lv.nodes * lv.B <= 0x7fffffffull;
+}
+PoolFetch pool_fetch(const CircuitLevel& lv) { return PoolFetch{lv.pool_a, lv.pool_b, lv.desc, lv.B, lv.first}; }
+}  // namespace
+
+hipError_t launch_prep_ginx_pool(const GateArgs& g, const CircuitLevel& lv, uint16_t* idx, uint32_t* tvb, hipStream_t s) {
+    if (g.count == 0) return hipSuccess;
+    if (!pool_args_ok(g, lv)) return hipErrorInvalidValue;
+    const uint64_t total = (uint64_t)g.count * g.n;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_prep_ginx<PoolFetch>, dim3(blocks), dim3(256), 0, s, pool_fetch(lv), g, idx, tvb);
     return hipGetLastError();
 }
 
@@ -1464,9 +1523,9 @@ constexpr int kPrepWaves = 4;
 // offsets the nSkips logic gives in closed form per 64 positions (below).
 // NMAX: the largest ring dimension and LWE dimension the LDS arrays hold (1024: the 32-bit sets;
 // 2048: N = 2048 and n up to 2048 for the 64-bit accumulator)
-template <int NMAX>
+template <int NMAX, class F>
 __global__ void __launch_bounds__(64 * kPrepWaves)
-    k_prep_lmk_w(GateInputs in, GateArgs g, const int16_t* __restrict__ logGen, uint16_t* __restrict__ ops,
+    k_prep_lmk_w(F in, GateArgs g, const int16_t* __restrict__ logGen, uint16_t* __restrict__ ops,
                  uint32_t* __restrict__ nops, uint32_t* __restrict__ tvb, uint32_t maxops, uint32_t numAutoKeys) {
     __shared__ uint32_t s_start[kPrepWaves][NMAX + 1];
     __shared__ uint16_t s_fill[kPrepWaves][NMAX];
@@ -1482,7 +1541,7 @@ __global__ void __launch_bounds__(64 * kPrepWaves)
     for (uint32_t p = lane; p < N; p += 64) start[p] = 0;
     wave_lds_sync();
     for (uint32_t i = lane; i < n; i += 64) {
-        const uint32_t a    = combine(in, in.a, (size_t)gate * n + i, 0, qm, g.xor_double);
+        const uint32_t a    = in.a((size_t)gate * n + i, n, qm);
         const uint32_t aodd = ((M - a) & (M - 1)) | 1u;  // (0 - a_i) mod 2N, made odd
         const int32_t v     = logGen[aodd];
         const uint32_t p    = v == (int32_t)M ? Nh - 1                          // -1
@@ -1575,14 +1634,15 @@ __global__ void __launch_bounds__(64 * kPrepWaves)
     const uint32_t k = n + A;
     if (lane == 0) {
         nops[gate] = k;
-        tvb[gate]  = combine(in, in.b, gate, in.boff, qm, g.xor_double);
+        tvb[gate]  = in.b(gate, qm);
     }
 }
 
 // AP / DM: ops in (i, digit) order; per 64-item chunk each lane emits its 0..digitsR nonzero
 // digits at the count of lower lanes' ops (ballots per digit slot)
+template <class F>
 __global__ void __launch_bounds__(64 * kPrepWaves)
-    k_prep_dm_w(GateInputs in, GateArgs g, uint16_t* __restrict__ ops, uint32_t* __restrict__ nops,
+    k_prep_dm_w(F in, GateArgs g, uint16_t* __restrict__ ops, uint32_t* __restrict__ nops,
                 uint32_t* __restrict__ tvb, uint32_t maxops, uint32_t baseR, uint32_t digitsR) {
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t gate = blockIdx.x * kPrepWaves + wv;
@@ -1592,7 +1652,7 @@ __global__ void __launch_bounds__(64 * kPrepWaves)
     uint32_t k = 0;
     for (uint32_t c = 0; c < n; c += 64) {
         const uint32_t i = c + lane;
-        const uint32_t a = i < n ? (g.q - combine(in, in.a, (size_t)gate * n + i, 0, qm, g.xor_double)) & qm : 0u;
+        const uint32_t a = i < n ? (g.q - in.a((size_t)gate * n + i, n, qm)) & qm : 0u;
         uint32_t cnt = 0, aI = a;
         for (uint32_t d = 0; d < digitsR; ++d, aI /= baseR) cnt += (aI % baseR) ? 1u : 0u;
         uint32_t below = 0, total = 0;
@@ -1611,9 +1671,23 @@ __global__ void __launch_bounds__(64 * kPrepWaves)
     }
     if (lane == 0) {
         nops[gate] = k;
-        tvb[gate]  = combine(in, in.b, gate, in.boff, qm, g.xor_double);
+        tvb[gate]  = in.b(gate, qm);
     }
 }
+
+namespace {
+template <class F>
+hipError_t prep_lmk(const GateArgs& g, const F& in, const int16_t* logGen, uint16_t* ops, uint32_t* nops, uint32_t* tvb,
+                    uint32_t maxops, uint32_t numAutoKeys, hipStream_t s) {
+    if (g.n <= 1024 && g.N <= 1024)
+        hipLaunchKernelGGL((k_prep_lmk_w<1024, F>), dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves),
+                           0, s, in, g, logGen, ops, nops, tvb, maxops, numAutoKeys);
+    else
+        hipLaunchKernelGGL((k_prep_lmk_w<2048, F>), dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves),
+                           0, s, in, g, logGen, ops, nops, tvb, maxops, numAutoKeys);
+    return hipGetLastError();
+}
+}  // namespace
 
 hipError_t launch_prep_lmk(const GateArgs& g, const GateInputs& in, const int16_t* logGen,
                            uint16_t* ops, uint32_t* nops, uint32_t* tvb, uint32_t maxops, uint32_t numAutoKeys,
@@ -1621,13 +1695,15 @@ hipError_t launch_prep_lmk(const GateArgs& g, const GateInputs& in, const int16_
     if (g.count == 0) return hipSuccess;
     if (in.k < 1 || in.k > 4 || numAutoKeys == 0) return hipErrorInvalidValue;
     if (g.n > 2048 || (g.N != 512 && g.N != 1024 && g.N != 2048)) return hipErrorInvalidValue;  // LDS sizes
-    if (g.n <= 1024 && g.N <= 1024)
-        hipLaunchKernelGGL(k_prep_lmk_w<1024>, dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves), 0,
-                           s, in, g, logGen, ops, nops, tvb, maxops, numAutoKeys);
-    else
-        hipLaunchKernelGGL(k_prep_lmk_w<2048>, dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves), 0,
-                           s, in, g, logGen, ops, nops, tvb, maxops, numAutoKeys);
-    return hipGetLastError();
+    return prep_lmk(g, ColumnFetch{in, g.xor_double}, logGen, ops, nops, tvb, maxops, numAutoKeys, s);
+}
+
+hipError_t launch_prep_lmk_pool(const GateArgs& g, const CircuitLevel& lv, const int16_t* logGen, uint16_t* ops,
+                                uint32_t* nops, uint32_t* tvb, uint32_t maxops, uint32_t numAutoKeys, hipStream_t s) {
+    if (g.count == 0) return hipSuccess;
+    if (!pool_args_ok(g, lv) || numAutoKeys == 0) return hipErrorInvalidValue;
+    if (g.n > 2048 || (g.N != 512 && g.N != 1024 && g.N != 2048)) return hipErrorInvalidValue;  // LDS sizes
+    return prep_lmk(g, pool_fetch(lv), logGen, ops, nops, tvb, maxops, numAutoKeys, s);
 }
 
 hipError_t launch_blind_rotate_lmk(const GateArgs& g, const BootTables& t, const void* bsk, const void* autok,
@@ -1664,8 +1740,19 @@ hipError_t launch_prep_dm(const GateArgs& g, const GateInputs& in, uint16_t* ops
     if (in.k < 1 || in.k > 4 || (size_t)g.n * digitsR > maxops || (size_t)g.n * baseR * digitsR > 0x8000u)
         return hipErrorInvalidValue;
     if (digitsR > 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_prep_dm_w, dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves), 0, s, in, g,
-                       ops, nops, tvb, maxops, baseR, digitsR);
+    hipLaunchKernelGGL(k_prep_dm_w<ColumnFetch>, dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves), 0,
+                       s, ColumnFetch{in, g.xor_double}, g, ops, nops, tvb, maxops, baseR, digitsR);
+    return hipGetLastError();
+}
+
+hipError_t launch_prep_dm_pool(const GateArgs& g, const CircuitLevel& lv, uint16_t* ops, uint32_t* nops, uint32_t* tvb,
+                               uint32_t maxops, uint32_t baseR, uint32_t digitsR, hipStream_t s) {
+    if (g.count == 0) return hipSuccess;
+    if (!pool_args_ok(g, lv) || (size_t)g.n * digitsR > maxops || (size_t)g.n * baseR * digitsR > 0x8000u)
+        return hipErrorInvalidValue;
+    if (digitsR > 8) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_prep_dm_w<PoolFetch>, dim3((g.count + kPrepWaves - 1) / kPrepWaves), dim3(64 * kPrepWaves), 0, s,
+                       pool_fetch(lv), g, ops, nops, tvb, maxops, baseR, digitsR);
     return hipGetLastError();
 }
 

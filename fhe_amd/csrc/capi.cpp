@@ -37,6 +37,8 @@ int guarded(F&& f) {
         return f();
     } catch (const HipError& e) {
         return fail(FHE_HIP_ERR_DEVICE, e.what());
+    } catch (const AllocError& e) {
+        return fail(FHE_HIP_ERR_ALLOC, e.what());
     } catch (const std::logic_error& e) {
         if (dynamic_cast<const std::invalid_argument*>(&e)) return fail(FHE_HIP_ERR_INVALID_PARAM, e.what());
         return fail(FHE_HIP_ERR_NOT_INIT, e.what());
@@ -110,6 +112,10 @@ struct CallOrder {
     }
     CallOrder(const CallOrder&) = delete;
     CallOrder& operator=(const CallOrder&) = delete;
+};
+
+struct fhe_hip_circuit {
+    Circuit c;
 };
 
 struct fhe_hip_multi {
@@ -1097,6 +1103,154 @@ int fhe_hip_encrypt_large(int paramset, int method, const uint64_t* skN, const i
     return guarded([&]() -> int {
         Params p = make_params(paramset, method);
         encrypt(p, skN, bits, count, seed, a, b, ptmod, p.Q, p.N);
+        return FHE_HIP_OK;
+    });
+}
+
+// ---- boolean circuits (circuit.h, circuit_engine.cpp) ----
+int fhe_hip_circuit_create(fhe_hip_circuit** out) {
+    if (!out) return fail(FHE_HIP_ERR_NULL_PTR, "out is null");
+    return guarded([&]() -> int {
+        *out = new fhe_hip_circuit();
+        return FHE_HIP_OK;
+    });
+}
+
+void fhe_hip_circuit_destroy(fhe_hip_circuit* c) { delete c; }
+
+int fhe_hip_circuit_add_input(fhe_hip_circuit* c, uint32_t* id) {
+    if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_input();
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_add_not(fhe_hip_circuit* c, uint32_t x, uint32_t* id) {
+    if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_not(x);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_add_gate(fhe_hip_circuit* c, int gate, uint32_t x, uint32_t y, uint32_t* id) {
+    if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_gate(gate, x, y);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_add_cmux(fhe_hip_circuit* c, uint32_t c0, uint32_t c1, uint32_t sel, uint32_t* id) {
+    if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_cmux(c0, c1, sel);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_add_bootstrap(fhe_hip_circuit* c, uint32_t x, uint32_t* id) {
+    if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_bootstrap(x);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_mark_output(fhe_hip_circuit* c, uint32_t id) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    return guarded([&]() -> int {
+        c->c.mark_output(id);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_finalize(fhe_hip_circuit* c) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    return guarded([&]() -> int {
+        c->c.finalize();
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_set_max_slots(fhe_hip_circuit* c, size_t max_slots) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    c->c.set_max_slots(max_slots);
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_circuit_counts(const fhe_hip_circuit* c, size_t* n_inputs, size_t* n_outputs, size_t* n_levels,
+                           size_t* n_bootstraps) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    if ((n_levels || n_bootstraps) && !c->c.finalized()) return fail(FHE_HIP_ERR_NOT_INIT, "circuit is not finalized");
+    if (n_inputs) *n_inputs = c->c.num_inputs();
+    if (n_outputs) *n_outputs = c->c.num_outputs();
+    if (n_levels) *n_levels = c->c.num_levels();
+    if (n_bootstraps) *n_bootstraps = c->c.num_bootstraps();
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_circuit_level(const fhe_hip_circuit* c, size_t level, size_t* width, size_t* first_row) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    return guarded([&]() -> int {
+        const size_t w = c->c.level_width(level), r = c->c.level_row(level);
+        if (width) *width = w;
+        if (first_row) *first_row = r;
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_node_row(const fhe_hip_circuit* c, uint32_t id, uint32_t* row, uint32_t* negated) {
+    if (!c || !row || !negated) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        c->c.node_row(id, row, negated);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_gate_fold(int paramset, int method, int gate, int ref_gate, uint32_t* dbl, uint64_t* bshift, uint64_t* q1) {
+    if (!dbl || !bshift || !q1) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        const GateFold f = gate_fold(make_params(paramset, method), gate, ref_gate);
+        *dbl = f.dbl;
+        *bshift = f.bshift;
+        *q1 = f.q1;
+        return FHE_HIP_OK;
+    });
+}
+
+// the circuit's own state is checked before the context, so these refusals need no device
+static int circuit_call_ok(const fhe_hip_circuit* c, uint32_t n_in, uint32_t n_out) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    if (!c->c.finalized()) return fail(FHE_HIP_ERR_NOT_INIT, "circuit is not finalized");
+    if (n_in != c->c.num_inputs() || n_out != c->c.num_outputs())
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "circuit has " + std::to_string(c->c.num_inputs()) + " inputs and " +
+                                                   std::to_string(c->c.num_outputs()) + " outputs");
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_eval_circuit_batch(fhe_hip_ctx* ctx, const fhe_hip_circuit* c, size_t count, uint32_t n_in, const uint64_t* a_in,
+                               const uint64_t* b_in, uint32_t n_out, uint64_t* a_out, uint64_t* b_out) {
+    if (const int e = circuit_call_ok(c, n_in, n_out)) return e;
+    if (!ctx || (count && ((n_in && (!a_in || !b_in)) || (n_out && (!a_out || !b_out)))))
+        return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        ctx_stream(ctx, nullptr);
+        ctx->eng.eval_circuit_host(c->c, count, a_in, b_in, a_out, b_out);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_eval_circuit_batch_device(fhe_hip_ctx* ctx, const fhe_hip_circuit* c, size_t count, uint32_t n_in,
+                                      const uint64_t* d_a_in, const uint64_t* d_b_in, uint32_t n_out, uint64_t* d_a_out,
+                                      uint64_t* d_b_out, void* stream) {
+    if (const int e = circuit_call_ok(c, n_in, n_out)) return e;
+    if (!ctx || (count && ((n_in && (!d_a_in || !d_b_in)) || (n_out && (!d_a_out || !d_b_out)))))
+        return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        const CallOrder order(ctx, stream);
+        ctx->eng.eval_circuit_device(c->c, count, d_a_in, d_b_in, d_a_out, d_b_out, order.s);
         return FHE_HIP_OK;
     });
 }

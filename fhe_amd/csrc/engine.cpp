@@ -393,7 +393,8 @@ Engine::~Engine() {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     for (void* ptr : {(void*)d_tables_, d_bsk_, (void*)d_ksk_, (void*)d_idx_, (void*)d_tvb_, (void*)d_ext_a_,
-                      (void*)d_ext_b_, (void*)d_io_, (void*)d_l1_, (void*)d_mix_, (void*)d_mixio_, (void*)d_tvbuf_, (void*)d_fb_, (void*)d_logGen_, (void*)d_ops_, (void*)d_nops_,
+                      (void*)d_ext_b_, (void*)d_io_, (void*)d_l1_, (void*)d_mix_, (void*)d_mixio_, (void*)d_pool_,
+                      (void*)d_cdesc_, (void*)d_cio_, (void*)d_tvbuf_, (void*)d_fb_, (void*)d_logGen_, (void*)d_ops_, (void*)d_nops_,
                       d_wtables_, (void*)d_wksk_, (void*)d_wext_a_, (void*)d_wext_b_,
                       (void*)d_epk_, (void*)d_epops_, (void*)d_epn_, d_bsk2_, (void*)d_kspart_, d_tables2k_,
                       (void*)d_ksk32_})

@@ -27,6 +27,10 @@ struct HipError : std::runtime_error {
     HipError(hipError_t e, const std::string& what)
         : std::runtime_error(what + ": " + hipGetErrorString(e)), code(e) {}
 };
+// a device workspace that would not fit the device's free memory (FHE_HIP_ERR_ALLOC)
+struct AllocError : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
 #define FHE_HIP_CHECK(expr)                                   \
     do {                                                      \
         hipError_t _e = (expr);                               \
@@ -124,6 +128,19 @@ public:
                         hipStream_t s);
     void eval_cmux_device(size_t count, const uint64_t* a0, const uint64_t* b0, const uint64_t* a1, const uint64_t* b1,
                           const uint64_t* a2, const uint64_t* b2, uint64_t* a_out, uint64_t* b_out, hipStream_t s);
+
+    // ---- boolean circuits (circuit.h; circuit_engine.cpp) ----
+    // B independent instances of a finalized circuit, level by level on the device: per level one indexed prep
+    // over all of its gates (any mix of 2-input types and BOOTSTRAP nodes, operands read by row from the
+    // ciphertext pool), one blind rotation with AND's window, one key switch straight into the level's block of
+    // pool rows; levels wider than a chunk (max_batch(), or the circuit's max_slots) run in contiguous chunks of
+    // slots.  a_in [n_in][B][n], b_in [n_in][B] mod q; a_out [n_out][B][n], b_out [n_out][B].  Device pointers,
+    // everything enqueued on s with no host synchronisation between levels.  AllocError when the pool
+    // (num_rows() B ciphertexts, no row reuse) would not fit the device's free memory.
+    void eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_in, const uint64_t* b_in, uint64_t* a_out,
+                             uint64_t* b_out, hipStream_t s);
+    void eval_circuit_host(const Circuit& c, size_t B, const uint64_t* a_in, const uint64_t* b_in, uint64_t* a_out,
+                           uint64_t* b_out);
 
     // ---- ciphertexts mod Q as inputs (binfhe-base-scheme.cpp:92-93, 150-152, 200-201) ----
     // SwitchCTtoqn (lwe-pke.cpp:170-178) of `count` ciphertexts a [count][N], b [count] mod Q into
@@ -299,6 +316,15 @@ private:
     // CMUX: first-level NAND outputs [2 count][n] + [2 count] (ccap_: bytes)
     size_t ccap_ = 0;
     uint64_t* d_l1_ = nullptr;
+    // circuits: the ciphertext pool [rows][n] ++ [rows] and the descriptors (CircuitSlot[] ++ CircuitOut[]) of the
+    // circuit being evaluated; host staging of eval_circuit_host
+    size_t poolcap_ = 0, cdesccap_ = 0, ciocap_ = 0;
+    uint64_t cdesc_serial_ = 0;   // Circuit::serial() of the descriptors resident in d_cdesc_
+    uint64_t* d_pool_ = nullptr;
+    uint64_t* d_cdesc_ = nullptr;
+    uint64_t* d_cio_ = nullptr;
+    // prep of slots [first, first + g.count) of a circuit level into workspace slots [0, g.count)
+    void prep_level_device(const GateArgs& g, const CircuitLevel& lv, hipStream_t s);
     // mixed-modulus inputs: switched columns (eval_mixed_device) and the host entry point's staging
     size_t mixcap_ = 0, mixiocap_ = 0;
     uint64_t* d_mix_ = nullptr;

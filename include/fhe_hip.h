@@ -331,6 +331,65 @@ int fhe_hip_unpack_keys(int paramset, int method, const uint8_t* bsk_packed, siz
                         size_t bsk_cap, const uint8_t* ksk_packed, size_t ksk_size, uint64_t* kskA, size_t kskA_cap,
                         uint64_t* kskB, size_t kskB_cap);
 
+/* ---- boolean circuits: the reference's BatchDAG (src/binfhe/include/batch/binfhe-batch.h:229-279), whose
+ * Execute runs one gate at a time (src/binfhe/lib/batch/batch.cpp:429-482) ----
+ * A circuit is a DAG built on the host (no context, no device).  Nodes get consecutive ids from 0 in the order
+ * they are added, returned in *id; operands must be existing ids.
+ *   input      a circuit input (a ciphertext mod q, dimension n)
+ *   not        EvalNOT (binfhe-base-scheme.cpp:223-236): costs no bootstrap, folded into its users
+ *   gate       OR, AND, NOR, NAND, XOR, XNOR, XOR_FAST, XNOR_FAST on two nodes
+ *   cmux       sel ? c1 : c0 = NAND(NAND(c0, NOT sel), NAND(c1, sel)) (:172-182): three bootstraps, two levels
+ *   bootstrap  BinFHEScheme::Bootstrap (:190-218)
+ * Any node can be marked as an output, any number of times; outputs come back in marking order.
+ * finalize levelises the DAG (inputs level 0; a bootstrapped node one more than its operands' highest level; a
+ * NOT the level of its source) and gives every level's nodes one contiguous block of rows in the evaluation's
+ * ciphertext pool (inputs first).  Evaluation runs level by level: one prep + blind rotation + key switch over
+ * ALL gates of a level, whatever their types, times `count` independent instances (DESIGN.md §4 "Circuits").
+ * Not supported (FHE_HIP_ERR_INVALID_PARAM when added): MAJORITY / AND3 / OR3 / AND4 / OR4 nodes, EvalFunc nodes,
+ * inputs mod Q.
+ * Errors: FHE_HIP_ERR_INVALID_PARAM for an unknown id, an unsupported gate code, gate(g, x, x) on the same
+ * (node, negation) -- the reference's ct1 == ct2 check (:85-86); gate(AND, x, not x) is accepted -- and any add /
+ * mark_output / finalize on a finalized circuit; FHE_HIP_ERR_NOT_INIT for a plan query or an evaluation before
+ * finalize. */
+typedef struct fhe_hip_circuit fhe_hip_circuit;
+int fhe_hip_circuit_create(fhe_hip_circuit** out);
+void fhe_hip_circuit_destroy(fhe_hip_circuit* c);
+int fhe_hip_circuit_add_input(fhe_hip_circuit* c, uint32_t* id);
+int fhe_hip_circuit_add_not(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
+int fhe_hip_circuit_add_gate(fhe_hip_circuit* c, int gate, uint32_t x, uint32_t y, uint32_t* id);
+int fhe_hip_circuit_add_cmux(fhe_hip_circuit* c, uint32_t c0, uint32_t c1, uint32_t sel, uint32_t* id);
+int fhe_hip_circuit_add_bootstrap(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
+int fhe_hip_circuit_mark_output(fhe_hip_circuit* c, uint32_t id);
+int fhe_hip_circuit_finalize(fhe_hip_circuit* c);
+/* slots (gates x instances) per launch: 0 = fhe_hip_max_batch_size; a smaller value cuts wider levels into
+ * contiguous chunks of slots (results are the same).  May be changed between evaluations. */
+int fhe_hip_circuit_set_max_slots(fhe_hip_circuit* c, size_t max_slots);
+/* any pointer may be NULL; n_levels (bootstrapped levels, the inputs' level 0 not counted) and n_bootstraps need a
+ * finalized circuit */
+int fhe_hip_circuit_counts(const fhe_hip_circuit* c, size_t* n_inputs, size_t* n_outputs, size_t* n_levels,
+                           size_t* n_bootstraps);
+/* level 0 .. n_levels (0: the inputs): its number of nodes and the pool row of its first node */
+int fhe_hip_circuit_level(const fhe_hip_circuit* c, size_t level, size_t* width, size_t* first_row);
+/* the pool row node id resolves to, and whether it is that row's EvalNOT (a NOT chain collapses onto its source) */
+int fhe_hip_circuit_node_row(const fhe_hip_circuit* c, uint32_t id, uint32_t* row, uint32_t* negated);
+/* `count` independent instances of the circuit.  a_in [n_in][count][n], b_in [n_in][count] mod q (input j =
+ * the j-th add_input); a_out [n_out][count][n], b_out [n_out][count].  n_in / n_out must be the circuit's counts.
+ * The circuit is checked before the context (NULL circuit, not finalized, wrong counts), so those refusals need
+ * no device.  FHE_HIP_ERR_ALLOC when the pool ((n_in + bootstraps) * count ciphertexts; rows are not reused)
+ * would not fit the device's free memory (fhe_hip_device_memory). */
+int fhe_hip_eval_circuit_batch(fhe_hip_ctx* ctx, const fhe_hip_circuit* c, size_t count, uint32_t n_in,
+                               const uint64_t* a_in, const uint64_t* b_in, uint32_t n_out, uint64_t* a_out,
+                               uint64_t* b_out);
+/* device buffers, asynchronous on stream: every level is enqueued with no host synchronisation in between */
+int fhe_hip_eval_circuit_batch_device(fhe_hip_ctx* ctx, const fhe_hip_circuit* c, size_t count, uint32_t n_in,
+                                      const uint64_t* d_a_in, const uint64_t* d_b_in, uint32_t n_out,
+                                      uint64_t* d_a_out, uint64_t* d_b_out, void* stream);
+/* How a level's gates share one launch (host only): gate's q1 = GetGateConst (rgsw-cryptoparameters.cpp:78-92),
+ * whether its input sum is doubled (XOR / XNOR), and bshift = q1(ref_gate) - q1(gate) mod q.  BootstrapGateCore's
+ * test vector (:535-567) of `gate` at b equals that of ref_gate at b + bshift, because the six 2-input gates
+ * differ only in where the half-circle window [q1, q1 + q/2) starts. */
+int fhe_hip_gate_fold(int paramset, int method, int gate, int ref_gate, uint32_t* dbl, uint64_t* bshift, uint64_t* q1);
+
 /* LWEEncryptionScheme::KeySwitch (lwe-pke.cpp:348-372): (N, qKS) -> (n, qKS) */
 int fhe_hip_keyswitch_batch(fhe_hip_ctx* ctx, size_t count, const uint64_t* a, const uint64_t* b, uint64_t* a_out,
                             uint64_t* b_out);
