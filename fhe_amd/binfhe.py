@@ -156,6 +156,11 @@ def _setup(L):
     L.fhe_hip_circuit_add_gate.argtypes = [vp, ctypes.c_int, u32, u32, pu32]
     L.fhe_hip_circuit_add_cmux.argtypes = [vp, u32, u32, u32, pu32]
     L.fhe_hip_circuit_add_bootstrap.argtypes = [vp, u32, pu32]
+    L.fhe_hip_circuit_add_func.argtypes = [vp, u32, vp, sz, pu32]
+    L.fhe_hip_circuit_add_linear.argtypes = [vp, vp, vp, u32, ctypes.c_uint64, pu32]
+    L.fhe_hip_circuit_level_classes.argtypes = [vp, sz, psz]
+    L.fhe_hip_circuit_func_class.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_int)]
+    L.fhe_hip_circuit_tables.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, sz, psz, psz]
     L.fhe_hip_circuit_mark_output.argtypes = [vp, u32]
     L.fhe_hip_circuit_finalize.argtypes = [vp]
     L.fhe_hip_circuit_set_max_slots.argtypes = [vp, sz]
@@ -416,8 +421,9 @@ def gate_fold(paramset, method, gate, ref_gate=AND):
 
 
 class Circuit:
-    """A boolean circuit (fhe_hip_circuit): a DAG of inputs, 2-input gates, NOT, CMUX and BOOTSTRAP nodes built on
-    the host, evaluated level by level on the GPU by GateEngine.eval_circuit.  Node ids are consecutive from 0.
+    """A circuit (fhe_hip_circuit): a DAG of inputs, 2-input gates, NOT, CMUX, BOOTSTRAP, FUNC (EvalFunc with a
+    LUT) and LINEAR (signed sum plus a constant) nodes built on the host, evaluated level by level on the GPU by
+    GateEngine.eval_circuit.  Node ids are consecutive from 0.
 
         c = Circuit()
         x, y = c.input(), c.input()
@@ -462,6 +468,46 @@ class Circuit:
 
     def bootstrap(self, x):
         return self._add(L().fhe_hip_circuit_add_bootstrap, x)
+
+    def func(self, x, lut):
+        """EvalFunc(x, lut): len(lut) a power of two >= 4 (the evaluating context's q), values < len(lut); x must
+        not be a NOT.  One bootstrap for a negacyclic LUT, two (two levels) for a periodic or an arbitrary one."""
+        lut = _u64(lut).reshape(-1)
+        return self._add(L().fhe_hip_circuit_add_func, x, ptr(lut), lut.size)
+
+    def linear(self, xs, signs=None, const=0):
+        """sum_j signs[j] xs[j] + (0, const) mod q over 1 to 4 nodes (signs +1 / -1, default all +1): no bootstrap.
+        An operand may be a NOT, never another linear node."""
+        xs = [int(x) for x in xs]
+        ax = (ctypes.c_uint32 * max(len(xs), 1))(*xs)
+        sg = None
+        if signs is not None:
+            signs = [int(v) for v in signs]
+            if len(signs) != len(xs):
+                raise ValueError("linear: one sign per operand")
+            sg = (ctypes.c_int * max(len(xs), 1))(*signs)
+        return self._add(L().fhe_hip_circuit_add_linear, ax, sg, len(xs), int(const) % (1 << 64))
+
+    def func_class(self, x):
+        """0 negacyclic, 1 periodic, 2 arbitrary for a func node, -1 otherwise"""
+        v = ctypes.c_int()
+        check(L().fhe_hip_circuit_func_class(self._h, x, ctypes.byref(v)))
+        return v.value
+
+    def level_classes(self, i):
+        """level i's rows in row order: (gates and BOOTSTRAP, tables at q, tables at 2q, linear)"""
+        w = (ctypes.c_size_t * 4)()
+        check(L().fhe_hip_circuit_level_classes(self._h, i, w))
+        return tuple(w)
+
+    def tables(self, paramset, method, cls):
+        """the distinct scaled test-vector tables of launch class cls (1: at q, 2: at 2q) as [n_tables][ctmod]"""
+        nt, cm = ctypes.c_size_t(), ctypes.c_size_t()
+        check(L().fhe_hip_circuit_tables(self._h, paramset, method, cls, None, 0, ctypes.byref(nt), ctypes.byref(cm)))
+        out = np.zeros((nt.value, cm.value), np.uint64)
+        if out.size:
+            check(L().fhe_hip_circuit_tables(self._h, paramset, method, cls, ptr(out), out.size, None, None))
+        return out
 
     def output(self, x):
         check(L().fhe_hip_circuit_mark_output(self._h, x))

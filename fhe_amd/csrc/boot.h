@@ -89,7 +89,9 @@ struct GateArgs {
     // accumulator still goes to acc_io
     uint32_t acc_tv;
     // BootstrapFunc with several tables (EvalFuncMultiOutputBatch, batch.cpp:141-174): tv_mod > 1 cycles
-    // gate g through table g % tv_mod, at tv + (g % tv_mod) ctmod (tv64 likewise); 0 / 1: the one table
+    // gate g through table g % tv_mod, at tv + (g % tv_mod) ctmod (tv64 likewise); 0 / 1: the one table.
+    // Circuits: the slot's table index in the high half of tvb[g] (b < ctmod <= 4096 is its low half) is added
+    // to that; every prep but PoolFetch's table slots writes zero there
     uint32_t tv_mod;
 };
 
@@ -108,11 +110,13 @@ struct GateInputs {
 // GINX/CGGI: inputs -> monomial exponents + test-vector b
 hipError_t launch_prep_ginx(const GateArgs& g, const GateInputs& in, uint16_t* idx, uint32_t* tvb, hipStream_t s);
 
-// One level of a circuit (circuit.h) as prep input: B instances of `nodes` gates of any 2-input types (and
-// BOOTSTRAP nodes), operands read by row from the ciphertext pool pool_a [rows][n] / pool_b [rows] (u64, mod q).
-// Slot s of the level is node s / B, instance s % B, its operands the rows src B + instance of desc[node];
-// a launch covers slots [first, first + g.count).  The launch's GateArgs are AND's: every node's window is
-// moved onto it by its bshift (DESIGN.md §4 "Circuits").
+// One launch class of a circuit level (circuit.h) as prep input: B instances of `nodes` slots, operands read by
+// row from the ciphertext pool pool_a [rows][n] / pool_b [rows] (u64, mod q; a class-2 first stage's row mod 2q).
+// Slot s of the class is node s / B, instance s % B, its operands the rows src B + instance of desc[node];
+// a launch covers slots [first, first + g.count).  Class 0 (gates of any 2-input types and BOOTSTRAP nodes): the
+// launch's GateArgs are AND's, every node's window is moved onto it by its bshift.  Classes 1 and 2 (FUNC
+// nodes): GateArgs with the class's tables in tv / tv64 and its ctmod; the prep writes each slot's table index
+// into the high half of tvb (DESIGN.md §4 "Circuits").
 struct CircuitLevel {
     const uint64_t* pool_a;
     const uint64_t* pool_b;
@@ -129,6 +133,10 @@ hipError_t launch_prep_dm_pool(const GateArgs& g, const CircuitLevel& lv, uint16
 // EvalNOT (binfhe-base-scheme.cpp:223-236: (-a, q/4 - b) mod q) applied where outs[o].neg
 hipError_t launch_circuit_gather(const uint64_t* pool_a, const uint64_t* pool_b, const CircuitOut* outs, uint32_t n_out,
                                  uint32_t B, uint32_t n, uint32_t q, uint64_t* a_out, uint64_t* b_out, hipStream_t s);
+// a level's LINEAR rows (circuit_gather.hip): pool row row0 + j = the signed sum desc[j] describes, mod q (a power
+// of two), for B instances; one launch over nodes x B x (n + 1) words
+hipError_t launch_circuit_linear(uint64_t* pool_a, uint64_t* pool_b, const CircuitLinear* desc, uint32_t nodes, uint32_t B,
+                                 uint32_t n, uint32_t q, uint32_t row0, hipStream_t s);
 // GINX with two waves per gate (one RLWE component each): keys repacked from the resident GINX
 // layout (launch_repack_ginx2); launched for gate batches with Q < 2^27 and ciphertext modulus q < 2N
 hipError_t launch_repack_ginx2(const void* bsk, uint32_t n, void* bsk2, hipStream_t s);
@@ -238,7 +246,7 @@ hipError_t launch_keyswitch_w32(const GateArgs& g, uint32_t baseKS, uint32_t dig
                                 const uint32_t* ms_a, const uint32_t* ms_b, uint64_t q_out, uint64_t* a_out,
                                 uint64_t* b_out, hipStream_t s, uint32_t* part = nullptr, size_t part_words = 0);
 // LWE element-wise operations on [count][len] / [count] u64 arrays (lwe.hip):
-//   reduce: (a, b) mod m (LWECiphertextImpl::SetModulus, lwe-ciphertext.h:116-120)
+//   reduce: (a, b) mod m (LWECiphertextImpl::SetModulus, lwe-ciphertext.h:116-120); outputs may alias
 //   sub:    x - y mod m, inputs < m (EvalSubEq / EvalSubEq2, lwe-pke.cpp:234-242); outputs may alias
 //   addb:   b = (b + c) mod m, c < m (EvalAddConstEq / EvalSubConstEq as m - c, :230-246)
 hipError_t launch_lwe_reduce(const uint64_t* a, const uint64_t* b, uint64_t* ao, uint64_t* bo, uint64_t m,

@@ -709,7 +709,8 @@ struct PoolFetch {
         const CircuitSlot d = desc[node];
         const uint32_t v = sum(d, (uint32_t)pb[(size_t)d.src0 * B + inst], (uint32_t)pb[(size_t)d.src1 * B + inst],
                                d.boff_pre, qm);
-        return (v + d.bshift) & qm;
+        // table slots (FUNC nodes): the slot's table index travels in the high half of tvb (0 for gates)
+        return ((v + d.bshift) & qm) | (d.flags & CircuitSlot::kTableMask);
     }
 };
 }  // namespace
@@ -793,9 +794,9 @@ __global__ void __launch_bounds__(256, FHE_WAVES_PER_EU)
     if (ACCIO && !g.acc_tv) {
         acc_load(acc, g, gate, h, l, T.ninvR, m);
     } else {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod); circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             const uint32_t x = (uint32_t)(r << 5) | l;
@@ -1290,9 +1291,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
         // acc1 <- acc1(X^(2N-5)) (:99) on half 1 only: X^1 (the identity) on half 0
         if (!DM) automorphism_eval(acc, tile, l, h ? M - 5 : 1u);
     } else {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod); circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             const uint32_t x = (uint32_t)(r << 5) | l;
@@ -2305,9 +2306,9 @@ __global__ void __launch_bounds__(128 * GW) __attribute__((amdgpu_waves_per_eu(G
     if (ACCIO && !g.acc_tv) {
         acc_load_c(acc, g, gate, c, L, T.ninvR, m);
     } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod); circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
         uint32_t tv[1][16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -2569,8 +2570,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     if (ACCIO && !g.acc_tv) {
         acc_load_c(acc, g, gate, c, L, T.ninvR, m);
     } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
         uint32_t tv[1][16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -2832,9 +2833,10 @@ __global__ void __launch_bounds__(128 * GW) __attribute__((amdgpu_waves_per_eu(2
         acc_load_c(acc, g, gate, c, L, T.ninvR, m);
         if (c == 1) automorphism_c(acc, region, L, M - 5);   // acc1 <- acc1(X^(2N-5)) (:99)
     } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // BootstrapFuncCore's table g.tv (:596-608), EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // BootstrapFuncCore's table g.tv (:596-608), EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod);
+        // circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
         uint32_t tv[1][16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -3120,8 +3122,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
         acc_load_c(acc, g, gate, c, L, T.ninvR, m);
         if (c == 1) automorphism_c(acc, tile, L, M - 5);
     } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
         uint32_t tv[1][16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

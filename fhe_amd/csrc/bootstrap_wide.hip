@@ -390,9 +390,9 @@ __global__ void __launch_bounds__((1 << LOGN) / 4, A::kWaves)
             acc1[r] = (T)src[N + t + TH * r];
         }
     } else {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod); circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
 #pragma unroll
         for (int r = 0; r < S; ++r) {
             const uint32_t x = t + TH * r;
@@ -591,9 +591,9 @@ __global__ void __launch_bounds__((1 << LOGN) / 4, A::kOpsWaves)
             acc1[r] = (T)src[N + (DM ? t + TH * r : auto_src<LOGN>(t + TH * r, 2 * N - 5))];
         }
     } else {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod)
-        const uint32_t tvo = g.tv_mod > 1 ? (gate % g.tv_mod) * g.ctmod : 0u;
+        const uint32_t tw = tvb[gate], b = tw & 0xffffu, cm = g.ctmod - 1;
+        // EvalFuncMultiOutput: table gate % tv_mod (GateArgs::tv_mod); circuits: + the slot's table (tvb's high half)
+        const uint32_t tvo = ((g.tv_mod > 1 ? gate % g.tv_mod : 0u) + (tw >> 16)) * g.ctmod;
 #pragma unroll
         for (int r = 0; r < S; ++r) {
             const uint32_t x = t + TH * r;

@@ -1158,6 +1158,56 @@ int fhe_hip_circuit_add_bootstrap(fhe_hip_circuit* c, uint32_t x, uint32_t* id) 
     });
 }
 
+int fhe_hip_circuit_add_func(fhe_hip_circuit* c, uint32_t x, const uint64_t* lut, size_t len, uint32_t* id) {
+    if (!c || !id || !lut) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_func(x, lut, len);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_add_linear(fhe_hip_circuit* c, const uint32_t* xs, const int* signs, uint32_t k, uint64_t constant,
+                               uint32_t* id) {
+    if (!c || !id || (k && !xs)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_linear(xs, signs, k, constant);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_level_classes(const fhe_hip_circuit* c, size_t level, size_t widths[4]) {
+    if (!c || !widths) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (!c->c.finalized()) return fail(FHE_HIP_ERR_NOT_INIT, "circuit is not finalized");
+    return guarded([&]() -> int {
+        c->c.level_classes(level, widths);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_func_class(const fhe_hip_circuit* c, uint32_t id, int* cls) {
+    if (!c || !cls) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *cls = c->c.func_class(id);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_tables(const fhe_hip_circuit* c, int paramset, int method, int cls, uint64_t* out, size_t cap,
+                           size_t* n_tables, size_t* ctmod) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    return guarded([&]() -> int {
+        const Params p = make_params(paramset, method);
+        const std::vector<uint64_t> t = c->c.tables(p, cls);
+        if (n_tables) *n_tables = c->c.num_tables(cls);
+        if (ctmod) *ctmod = Circuit::table_ctmod(p, cls);
+        if (out) {
+            if (cap < t.size()) throw std::invalid_argument("circuit tables: the buffer is too small");
+            std::copy(t.begin(), t.end(), out);
+        }
+        return FHE_HIP_OK;
+    });
+}
+
 int fhe_hip_circuit_mark_output(fhe_hip_circuit* c, uint32_t id) {
     if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
     return guarded([&]() -> int {

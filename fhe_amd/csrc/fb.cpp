@@ -18,42 +18,8 @@ constexpr uint64_t kBeta = 128;  // BinFHEContext::GetBeta (binfhecontext.h:445-
 
 bool pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
-// test-vector functions f(x, q = ctmod, Q = fmod) of the reference's lambdas
-enum TvKind { TV_LUT, TV_LUT_ANTI, TV_HALF, TV_FLOOR2, TV_SIGN, TV_SIGN_SS };
-std::vector<uint64_t> tv_values(TvKind kind, const uint64_t* lut, uint64_t lutlen, uint64_t q, uint64_t fmod) {
-    std::vector<uint64_t> f(q);
-    for (uint64_t x = 0; x < q; ++x) {
-        switch (kind) {
-            case TV_LUT: f[x] = lut[x]; break;                                                       // :254-256
-            case TV_LUT_ANTI:                                                                        // :302-307, 324-329
-                f[x] = x < (q >> 1) ? lut[x % lutlen] : fmod - lut[(x - q / 2) % lutlen];
-                break;
-            case TV_HALF: f[x] = x < (q >> 1) ? fmod - (q >> 2) : (q >> 2); break;                  // f0/f1 :285-290
-            case TV_FLOOR2:                                                                          // f2 :361-368
-                f[x] = x < (q >> 2) ? fmod - (q >> 1) - x : (x < 3 * (q >> 2) ? x : fmod + (q >> 1) - x);
-                break;
-            case TV_SIGN: f[x] = x < q / 2 ? fmod / 4 : fmod - fmod / 4; break;                      // f3 :413-416
-            case TV_SIGN_SS: f[x] = x < q / 2 ? fmod - fmod / 4 : fmod / 4; break;                   // :421-424
-        }
-    }
-    return f;
-}
-
-// checkInputFunction (binfhe-base-scheme.h:245-260): 0 negacyclic, 1 periodic, 2 arbitrary
-int lut_property(const uint64_t* lut, uint64_t len, uint64_t mod) {
-    const uint64_t mid = len / 2;
-    if (lut[0] == mod - lut[mid]) {
-        for (uint64_t i = 1; i < mid; ++i)
-            if (lut[i] != mod - lut[mid + i]) return 2;
-        return 0;
-    }
-    if (lut[0] == lut[mid]) {
-        for (uint64_t i = 1; i < mid; ++i)
-            if (lut[i] != lut[mid + i]) return 2;
-        return 1;
-    }
-    return 2;
-}
+// the test-vector functions (tv_values) and checkInputFunction (lut_property) are circuit.h's: the circuit
+// plan builds the same tables
 }  // namespace
 
 uint64_t* Engine::fb_work(size_t count, int cts) {

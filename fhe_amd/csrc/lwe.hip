@@ -8,8 +8,9 @@
 namespace fhe_amd {
 
 namespace {
-__global__ void k_lwe_reduce(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint64_t* ao,
-                             uint64_t* bo, uint64_t m, uint64_t total, size_t count) {
+// outputs may alias the inputs (the circuit engine reduces pool rows in place)
+__global__ void k_lwe_reduce(const uint64_t* a, const uint64_t* b, uint64_t* ao, uint64_t* bo, uint64_t m, uint64_t total,
+                             size_t count) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x)
         ao[i] = a[i] % m;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x)

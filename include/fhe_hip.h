@@ -340,13 +340,18 @@ int fhe_hip_unpack_keys(int paramset, int method, const uint8_t* bsk_packed, siz
  *   gate       OR, AND, NOR, NAND, XOR, XNOR, XOR_FAST, XNOR_FAST on two nodes
  *   cmux       sel ? c1 : c0 = NAND(NAND(c0, NOT sel), NAND(c1, sel)) (:172-182): three bootstraps, two levels
  *   bootstrap  BinFHEScheme::Bootstrap (:190-218)
+ *   func       EvalFunc(x, lut) (:241-337): one bootstrap for a negacyclic LUT, two for a periodic or an arbitrary
+ *              one (two levels); FUNC nodes of one class on one operand share the first of the two
+ *   linear     sum of 1 to 4 nodes with signs, plus a constant on b, mod q (EvalAddEq / EvalSubEq /
+ *              EvalAddConstEq, lwe-pke.cpp:230-246): no bootstrap, a row of its own at its operands' highest level
  * Any node can be marked as an output, any number of times; outputs come back in marking order.
  * finalize levelises the DAG (inputs level 0; a bootstrapped node one more than its operands' highest level; a
  * NOT the level of its source) and gives every level's nodes one contiguous block of rows in the evaluation's
  * ciphertext pool (inputs first).  Evaluation runs level by level: one prep + blind rotation + key switch over
- * ALL gates of a level, whatever their types, times `count` independent instances (DESIGN.md §4 "Circuits").
- * Not supported (FHE_HIP_ERR_INVALID_PARAM when added): MAJORITY / AND3 / OR3 / AND4 / OR4 nodes, EvalFunc nodes,
- * inputs mod Q.
+ * ALL gates of a level, whatever their types, times `count` independent instances, one more such launch for the
+ * level's FUNC bootstraps at modulus q and one for those at 2q, then one element-wise launch for its linear nodes
+ * (DESIGN.md §4 "Circuits").
+ * Not supported (FHE_HIP_ERR_INVALID_PARAM when added): MAJORITY / AND3 / OR3 / AND4 / OR4 nodes, inputs mod Q.
  * Errors: FHE_HIP_ERR_INVALID_PARAM for an unknown id, an unsupported gate code, gate(g, x, x) on the same
  * (node, negation) -- the reference's ct1 == ct2 check (:85-86); gate(AND, x, not x) is accepted -- and any add /
  * mark_output / finalize on a finalized circuit; FHE_HIP_ERR_NOT_INIT for a plan query or an evaluation before
@@ -359,6 +364,17 @@ int fhe_hip_circuit_add_not(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
 int fhe_hip_circuit_add_gate(fhe_hip_circuit* c, int gate, uint32_t x, uint32_t y, uint32_t* id);
 int fhe_hip_circuit_add_cmux(fhe_hip_circuit* c, uint32_t c0, uint32_t c1, uint32_t sel, uint32_t* id);
 int fhe_hip_circuit_add_bootstrap(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
+/* lut[len], len a power of two >= 4, every value < len.  FHE_HIP_ERR_INVALID_PARAM otherwise, and when x resolves to
+ * a NOT (EvalNOT negates mod q, which does not survive an arbitrary LUT's lift to 2q: bootstrap it, or fold the
+ * NOT into the LUT).  The LUT's class (checkInputFunction, binfhe-base-scheme.h:245-260) is fixed here.  len must
+ * equal the evaluating context's q, and an arbitrary LUT needs q <= N and a method other than AP: both are only
+ * known at evaluation, which refuses with FHE_HIP_ERR_INVALID_PARAM. */
+int fhe_hip_circuit_add_func(fhe_hip_circuit* c, uint32_t x, const uint64_t* lut, size_t len, uint32_t* id);
+/* sum_j (signs[j] < 0 ? -1 : +1) xs[j] + (0, constant mod q), 1 <= k <= 4; signs NULL: all +.  An operand that
+ * resolves to a NOT folds in as a sign flip and +-q/4.  FHE_HIP_ERR_INVALID_PARAM for k out of range, an unknown
+ * id, or an operand that is itself a linear node (flatten the sum). */
+int fhe_hip_circuit_add_linear(fhe_hip_circuit* c, const uint32_t* xs, const int* signs, uint32_t k, uint64_t constant,
+                               uint32_t* id);
 int fhe_hip_circuit_mark_output(fhe_hip_circuit* c, uint32_t id);
 int fhe_hip_circuit_finalize(fhe_hip_circuit* c);
 /* slots (gates x instances) per launch: 0 = fhe_hip_max_batch_size; a smaller value cuts wider levels into
@@ -370,12 +386,23 @@ int fhe_hip_circuit_counts(const fhe_hip_circuit* c, size_t* n_inputs, size_t* n
                            size_t* n_bootstraps);
 /* level 0 .. n_levels (0: the inputs): its number of nodes and the pool row of its first node */
 int fhe_hip_circuit_level(const fhe_hip_circuit* c, size_t level, size_t* width, size_t* first_row);
+/* A level's rows in row order: widths[0..2] its bootstraps by launch class (0 gates and BOOTSTRAP, 1 tables at q,
+ * 2 tables at 2q with the first stages first; each class one contiguous block), widths[3] its linear rows.
+ * Level 0 holds the inputs (not counted here) and its linear rows. */
+int fhe_hip_circuit_level_classes(const fhe_hip_circuit* c, size_t level, size_t widths[4]);
+/* *cls = 0 negacyclic, 1 periodic, 2 arbitrary for a func node, -1 for any other; known as soon as it is added */
+int fhe_hip_circuit_func_class(const fhe_hip_circuit* c, uint32_t id, int* cls);
+/* The distinct test-vector tables launch class cls (1 or 2) holds for a parameter set (host only): *n_tables
+ * tables of *ctmod (q or 2q) words, (Q / ctmod) f(x) as BootstrapFuncCore scales them (:596-608).  out may be NULL
+ * to size it; otherwise cap (words) must hold them.  FHE_HIP_ERR_INVALID_PARAM as at evaluation (above). */
+int fhe_hip_circuit_tables(const fhe_hip_circuit* c, int paramset, int method, int cls, uint64_t* out, size_t cap,
+                           size_t* n_tables, size_t* ctmod);
 /* the pool row node id resolves to, and whether it is that row's EvalNOT (a NOT chain collapses onto its source) */
 int fhe_hip_circuit_node_row(const fhe_hip_circuit* c, uint32_t id, uint32_t* row, uint32_t* negated);
 /* `count` independent instances of the circuit.  a_in [n_in][count][n], b_in [n_in][count] mod q (input j =
  * the j-th add_input); a_out [n_out][count][n], b_out [n_out][count].  n_in / n_out must be the circuit's counts.
  * The circuit is checked before the context (NULL circuit, not finalized, wrong counts), so those refusals need
- * no device.  FHE_HIP_ERR_ALLOC when the pool ((n_in + bootstraps) * count ciphertexts; rows are not reused)
+ * no device.  FHE_HIP_ERR_ALLOC when the pool ((n_in + bootstraps + linear nodes) * count ciphertexts; rows are not reused)
  * would not fit the device's free memory (fhe_hip_device_memory). */
 int fhe_hip_eval_circuit_batch(fhe_hip_ctx* ctx, const fhe_hip_circuit* c, size_t count, uint32_t n_in,
                                const uint64_t* a_in, const uint64_t* b_in, uint32_t n_out, uint64_t* a_out,
