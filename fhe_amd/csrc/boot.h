@@ -1,5 +1,5 @@
 // boot.h -- device-side argument blocks and launchers for the gate bootstrap
-// (bootstrap.hip) and the LWE key switch (keyswitch.hip).
+// (bootstrap.hip, boot_n2k_*.hip) and the LWE key switch (keyswitch.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

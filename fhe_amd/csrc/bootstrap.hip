@@ -1,29 +1,39 @@
-// bootstrap.hip -- fused TFHE gate bootstrap (GINX / CGGI) for gfx950.
+// bootstrap.hip -- the fused blind rotations of the TFHE gate bootstrap at N = 1024 for gfx950, 32-bit residues:
+// the prep kernels, K1 (GINX, and the LMKCDEY / AP op-list kernel), the split kernels K1s, K1x, K1q and K1m, and
+// the ExternalProduct seam's helpers.  The N = 2048 kernels (K1w) are boot_n2k_ginx.hip and boot_n2k_lmk.hip; the
+// arithmetic both sides use is boot_arith.h.  Each family below opens with its own mapping, steps and bounds;
+// this header describes K1 GINX, k_blind_rotate_ginx.
 //
-// One wavefront per gate, for all n iterations of the accumulator loop
-// (RingGSWAccumulatorCGGI::EvalAcc, src/binfhe/lib/rgsw-acc-cggi.cpp:59-68):
-// the RLWE accumulator never leaves the CU.  Half-wave h (lanes 32h..32h+31)
-// owns polynomial component h (acc0 / acc1) as 32 registers x 32 lanes:
+// Mapping.  One wavefront owns one gate for all n iterations of the accumulator loop
+// (RingGSWAccumulatorCGGI::EvalAcc, rgsw-acc-cggi.cpp:59-68), four gates per 256-thread workgroup: the RLWE
+// accumulator never leaves the CU.  Half-wave h (lanes 32h..32h+31) owns component acc_h as 32 registers x 32 lanes:
 //   layout A' (COEFFICIENT): lane l, register r  <->  coefficient x = (r << 5) | l
 //   layout B' (EVALUATION):  lane l, register r  <->  NTT slot      x = (l << 5) | r
-// (slot x is the reference's bit-reversed EVALUATION storage index).  A forward
-// NTT runs 5 radix-2 stages in A' (twiddles uniform over the wave: scalar
-// loads), one 32x32 LDS transpose, 5 stages in B' (per-lane twiddles from an
-// LDS table laid out lane-major: conflict-free); the inverse runs backwards.
-// Per iteration (AddToAccCGGI, rgsw-acc-cggi.cpp:102-151):
-//   iNTT(acc0 | acc1) -> signed approximate decomposition (rgsw-acc.cpp:54-91)
-//   -> NTT(D0 | D1), NTT(D2 | D3) -> per slot, all four digits gathered with
-//   v_permlane32_swap -> S1 = sum_d D_d K+[d][h], S2 = sum_d D_d K-[d][h] as
-//   64-bit v_mad_u64_u32 sums (keys in Montgomery form) -> one Montgomery
-//   reduction each -> acc_h += S1 (X^a - 1) + S2 (X^-a - 1), the monomials
-//   EVAL(X^m - 1) = omega_slot^m - 1 read from a 2N-entry LDS table instead of
-//   the reference's 16 MiB table of 2N NTT'd polynomials
-//   (rgsw-cryptoparameters.cpp:96-113).
-// All arithmetic is exact mod Q: lazy residues (< 4Q) inside the NTTs, canonical
-// [0, Q) at every point where the reference's values are observable (COEF acc
-// before decomposition, EVAL acc between iterations, outputs).
-#include "arith.h"
-#include "boot.h"
+// (slot x is the reference's bit-reversed EVALUATION storage index).  A forward transform runs 5 radix-2 stages in
+// A' (twiddles uniform over the wave: scalar loads), one 32 x 32 LDS transpose (row stride 33), 5 stages in B'
+// (per-lane twiddles from an LDS table laid out lane-major: conflict-free); the inverse runs backwards.  Between
+// iterations acc is in B', scaled by N^-1 like the keys.
+// Per iteration (AddToAccCGGI, rgsw-acc-cggi.cpp:102-151), for LZ (Q < 2^27, signed residues):
+//   1. signed inverse pass of a copy of acc (|acc| < 2.8 Q, kAccBoundLZ); its last stage lands on d + C of the
+//      centred coefficient d (dec_leg, dec_leg2; FHE_DEC_TAIL) instead of a canonical value;
+//   2. SignedDigitDecompose (rgsw-acc.cpp:54-91): the two retained balanced digits as signed bit fields of
+//      d + C; half h holds D_h and D_{2+h};
+//   3. one signed forward pass of both digit polynomials (fwd_pass2 FM 1: the first two stages as one 4-point
+//      group, |D| < 10 Q + 2^(g-1) in EVAL, no reduction);
+//   4. per slot, the other half-wave's two digits by ds_bpermute (other_half); with the half-swapped key rows
+//      (boot.h kBskHalfSwap) every lane multiplies (own, other) digits in one order;
+//   5. S+- = sum_d D_d K+-_d as unreduced signed 64-bit sums (mac4: v_mad_i64_i32); the keys arrive as one
+//      16-byte vector (K+[2k], K+[2k+1], K-[2k], K-[2k+1]) per digit row and slot pair, FHE_KEY_PF pairs ahead;
+//   6. acc <- acc + S+ (w^a - 1) + S- (w^-a - 1) with one signed Montgomery reduction per slot: S m =
+//      lo(S) m + hi(S) (m 2^32) from the (plain, Montgomery) pair table of psi^e - 1 in LDS (instead of the
+//      reference's table of 2N transformed monomials, rgsw-cryptoparameters.cpp:96-113), acc folded in as
+//      acc (2^32 mod Q).  |acc| < 2.75 Q in and out.
+// Otherwise (2^27 <= Q < 2^28) the same steps on unsigned lazy residues: inv_pass to canonical coefficients,
+// digits offset by Q, fwd_pass2 FM 0 (< 16 Q), two Montgomery reductions of S+- and one of the monomial sum per
+// slot, acc kept in [0, 2 Q).
+// Before the loop: acc1 = NTT(test vector), acc0 = 0 (or both from GateArgs::acc_io).  After it: inverse pass to
+// canonical COEF, the extraction of binfhe-base-scheme.cpp:110-121 and, with msb_out, ModSwitch to qKS.
+#include "boot_arith.h"
 
 #ifndef FHE_KEY_PF
 #define FHE_KEY_PF 2     // key chunks (2 slots each) requested ahead of use in the CMUX loop
@@ -38,20 +48,10 @@
 #define FHE_K1_STAGGER 0  // A/B: odd workgroup slots start FHE_K1_STAGGER x 8128 cycles late
 #endif
 
-// Forward-transform bounds from the product itself (round 5): a signed Montgomery product is below
-// |y| |w| 2^-32 + Q/2 < (Q / 2^32) |y| + Q/2, so a Cooley-Tukey stage takes a bound B to (1 + Q / 2^32) B + Q/2
-// rather than B + Q.  From signed digits (B ~ 0): ten stages stay below 6.67 Q for Q < 2^28 (Q / 2^32 < 1/16),
-// inside the 8 Q of 32-bit signed words, so FM 2 needs no reduction (the LMKCDEY accumulator bound grows from
-// 2.0 Q to 2.2 Q: four digits < 6.67 Q times keys < Q, 26.7 Q^2 2^-32 + Q/2); and for Q < 2^29 (1/8) five
-// stages stay below 3.21 Q < 4 Q, so K1w's QM 2 reduces after five stages and after nine (below 0.9 Q each
-// time, 3.84 Q before the second) instead of after three, six and nine; for Q < 2^28 eleven stages stay below
-// 7.59 Q < 8 Q, so K1w's QM 1 (STD256Q_LMKCDEY) drops its one reduction.  FHE_FWD_TIGHT=0: the round-4 points.
-#ifndef FHE_FWD_TIGHT
-#define FHE_FWD_TIGHT 1
-#endif
 // The signed forward passes of K1 (fwd_pass2 FM 1 / 2, fwd_pass_s) run their first two stages as one 4-point
 // group with two products instead of three (fwd_group4): one signed Montgomery product less per group, at
-// half a Q more on the group's outputs.  For FM 2 that takes the 6.67 Q above to 7.43 Q (still inside 8 Q) and
+// half a Q more on the group's outputs.  For FM 2 that takes the 6.67 Q of FHE_FWD_TIGHT (boot_arith.h) to 7.43 Q
+// (still inside 8 Q) and
 // the LMKCDEY accumulator bound from 2.2 Q to 2.4 Q (four digits < 7.44 Q times keys < Q: 29.8 Q^2 2^-32 + Q/2
 // < 2.36 Q); make_inv_plan and make_inv_plan_ww give the same reductions for 2.4 Q as for 2.2 Q.
 // FHE_FWD_GROUP=0: ten radix-2 stages (A/B).
@@ -77,23 +77,6 @@ namespace {
 constexpr int kTile = 32 * 33;  // one half-wave transpose tile (u32 words)
 constexpr int kAccBoundLZ = 28; // GINX, Q < 2^27: |acc| < 2.8 Q between iterations (units of Q/10)
 
-struct Mod {
-    uint32_t Q, Q2, qinv;  // qinv = -Q^-1 mod 2^32
-    uint32_t qinvp;        // Q^-1 mod 2^32 (signed Montgomery)
-    int32_t nQ;            // -Q (signed Montgomery; see fresh_nq)
-    uint32_t oneR;         // 2^32 mod Q: smont_mul(x, oneR) = x mod Q in (-Q, Q)
-    uint32_t gpR, gmR;     // BootTables::gpR / gmR (fwd_group4)
-};
-FHE_DEV Mod make_mod(const BootTables& T) {
-    return Mod{T.Q, T.Q2, T.qinv, 0u - T.qinv, -(int32_t)T.Q, T.oneR, T.gpR, T.gmR};
-}
-
-// a * bR * 2^-32 mod Q, lazily: result < Q (1 + a / 2^32 * ...) < 2Q for a < 4Q, Q < 2^28
-FHE_DEV uint32_t mont_mul(uint32_t a, uint32_t bR, const Mod& m) {
-    uint64_t t  = (uint64_t)a * bR;
-    uint32_t mm = (uint32_t)t * m.qinv;
-    return (uint32_t)((t + (uint64_t)mm * m.Q) >> 32);
-}
 FHE_DEV uint32_t mont_red(uint64_t t, const Mod& m) {  // t < 16 Q^2 -> result < 2Q
     uint32_t mm = (uint32_t)t * m.qinv;
     return (uint32_t)((t + (uint64_t)mm * m.Q) >> 32);
@@ -118,62 +101,6 @@ FHE_DEV void ct_bf(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     uint32_t s = x + m.Q2;
     y          = s - t;
     x          = x + t;
-}
-#ifndef FHE_DM_WAVES
-#define FHE_DM_WAVES 3   // waves per SIMD of the AP/DM op-list kernel
-#endif
-#ifndef FHE_LMK_WAVES
-#define FHE_LMK_WAVES 2  // waves per SIMD of the LMKCDEY op-list kernel
-#endif
-#ifndef FHE_LMK_OPAQUE
-#define FHE_LMK_OPAQUE 0 // op-list kernel: per-lane addresses recomputed per op (register pressure)
-#endif
-#ifndef FHE_LMK_PRE
-#define FHE_LMK_PRE 1    // op-list kernel: a pass's 31 per-lane twiddles requested together at its start
-#endif
-#ifndef FHE_LMK_AKPF
-#define FHE_LMK_AKPF 1   // the same for the automorphism keys (4 slots x 2 rows)
-#endif
-#ifndef FHE_LMK_SWAP
-#define FHE_LMK_SWAP 1   // LMKCDEY automorphism: the digits into the half-wave layout by v_permlane32_swap
-#endif
-#ifndef FHE_LMK_ABL
-#define FHE_LMK_ABL 0    // timing-only ablations of the LMKCDEY op-list kernel (wrong results), bits: 1 every EXT op
-                         // reads the keys of index 0, 2 every AUTO op those of key 0 (cache-resident: the data-
-                         // dependent key traffic removed), 4 the automorphism gathers at linear positions, 8 no digit
-                         // exchange between the half-waves in EXT
-#endif
-#ifndef FHE_LMK_KPF
-#define FHE_LMK_KPF 1    // op-list kernel: key chunks (4 slots x 4 rows) requested ahead of their MAC
-#endif
-// v_mad_i64_i32 (a * b + c, 32 x 32 -> 64 signed) in plain C, with -Q re-materialised inside each
-// loop body (fresh_nq) so that instruction selection sees a sign-extended 32-bit operand (hoisted,
-// the compiler widens -Q into a 64-bit constant and the product becomes 5 instructions)
-FHE_DEV int64_t mad_i64_i32(int32_t a, int32_t b, int64_t c) {
-    return (int64_t)a * b + c;
-}
-// signed Montgomery (the Q < 2^27 path): a read as int32, bR < Q -> (a b 2^-32 mod Q) in (-Q, Q)
-// for any |a| < 2^31: |a bR - mm Q| < 2^31 Q + 2^31 Q
-FHE_DEV uint32_t smont_mul(uint32_t a, uint32_t bR, const Mod& m) {
-    const int64_t t  = mad_i64_i32((int32_t)a, (int32_t)bR, 0);
-    const int32_t mm = (int32_t)((uint32_t)t * m.qinvp);
-    return (uint32_t)(mad_i64_i32(mm, m.nQ, t) >> 32);
-}
-// signed Montgomery reduction of a 64-bit t, |t| < 2^63 - 2^31 Q: t 2^-32 mod Q in (|t| 2^-32 +- Q/2)
-FHE_DEV uint32_t smont_red(int64_t t, const Mod& m) {
-    const int32_t mm = (int32_t)((uint32_t)t * m.qinvp);
-    return (uint32_t)(mad_i64_i32(mm, m.nQ, t) >> 32);
-}
-// -Q as a value defined inside the current loop body (an empty asm the optimizer cannot hoist)
-FHE_DEV Mod fresh_nq(Mod m) {
-    asm volatile("" : "+s"(m.nQ));
-    return m;
-}
-// signed Cooley-Tukey: |x|, |y| < B in, < B + Q out, two adds and no offset
-FHE_DEV void ct_bf_s(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
-    const uint32_t t = smont_mul(y, wR, m);
-    y                = x - t;
-    x                = x + t;
 }
 // The first two signed forward stages (register bits 4 and 3: twiddles I = Table[1] everywhere, then
 // u = Table[2] below register 16 and v = Table[3] = I u above) on the group {a, b, c, d} = registers
@@ -202,13 +129,6 @@ FHE_DEV void gs_bf(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     uint32_t d = x + m.Q2 - y;
     x          = s;
     y          = mont_mul(d, wR, m);
-}
-
-// intra-wave LDS hand-off: orders this wave's LDS accesses around a layout change
-FHE_DEV void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 FHE_DEV void transpose32(uint32_t (&v)[32], uint32_t* tile, int l) {
@@ -624,15 +544,6 @@ FHE_DEV void dec_digits(uint32_t u, const Dec& c, uint32_t& dA, uint32_t& dB) {
     }
 }
 
-// ModSwitch RoundqQ (lwe-pke.cpp:41-46): floor(0.5 + v*to/from) mod to, in IEEE double in
-// the reference.  For v*to < 2^53, v < from and odd `from` (or power-of-two from/to) the
-// double expression never crosses a rounding boundary, so it equals the exact integer
-// floor((2 v to + from) / (2 from)) (proof in DESIGN.md, exhaustively tested).
-FHE_DEV uint32_t mod_switch(uint64_t v, uint64_t from, uint64_t to) {
-    uint64_t r = (2 * v * to + from) / (2 * from);
-    return (uint32_t)(r % to);
-}
-
 // accumulator I/O of the seam instantiations (GateArgs::acc_io): lane (h, l) register r holds
 // EVAL slot (l << 5) | r of component h.  In: canonical u64 -> N^-1-scaled residue (the keys carry
 // N^-1, BootTables::ninvR).  Out: any |acc| < 2^31 -> acc N mod Q, canonical u64.
@@ -1019,6 +930,37 @@ hipError_t launch_blind_rotate_ginx(const GateArgs& g, const BootTables& t, cons
 //                         with (*ek)[0][1][t]                              (:257-287)
 // k_prep_lmk_w builds them with a stable counting sort of the a_i into the
 // logGen groups (permuteMap, :83-94) and replays the nSkips logic (:99-157).
+// its knobs (LMKCDEY and, with DM, AP/DM)
+#ifndef FHE_DM_WAVES
+#define FHE_DM_WAVES 3   // waves per SIMD of the AP/DM op-list kernel
+#endif
+#ifndef FHE_LMK_WAVES
+#define FHE_LMK_WAVES 2  // waves per SIMD of the LMKCDEY op-list kernel
+#endif
+#ifndef FHE_LMK_OPAQUE
+#define FHE_LMK_OPAQUE 0 // op-list kernel: per-lane addresses recomputed per op (register pressure)
+#endif
+#ifndef FHE_LMK_PRE
+#define FHE_LMK_PRE 1    // op-list kernel: a pass's 31 per-lane twiddles requested together at its start
+#endif
+#ifndef FHE_LMK_AKPF
+#define FHE_LMK_AKPF 1   // the same for the automorphism keys (4 slots x 2 rows)
+#endif
+#ifndef FHE_LMK_SWAP
+#define FHE_LMK_SWAP 1   // LMKCDEY automorphism: the digits into the half-wave layout by v_permlane32_swap
+#endif
+#ifndef FHE_LMK_ABL
+#define FHE_LMK_ABL 0    // timing-only ablations of the LMKCDEY op-list kernel (wrong results), bits: 1 every EXT op
+                         // reads the keys of index 0, 2 every AUTO op those of key 0 (cache-resident: the data-
+                         // dependent key traffic removed), 4 the automorphism gathers at linear positions, 8 no digit
+                         // exchange between the half-waves in EXT
+#endif
+#if FHE_LMK_ABL && !defined(FHE_ALLOW_WRONG_RESULTS)
+#error "FHE_LMK_ABL builds a k_blind_rotate_lmk that computes wrong ciphertexts (timing-only ablation); add -DFHE_ALLOW_WRONG_RESULTS to build it anyway"
+#endif
+#ifndef FHE_LMK_KPF
+#define FHE_LMK_KPF 1    // op-list kernel: key chunks (4 slots x 4 rows) requested ahead of their MAC
+#endif
 namespace {
 // EVAL-domain automorphism X -> X^k (poly-impl.h:350-356 / PrecomputeAutoMap, nbtheory2.cpp:264-275):
 // out[slot brv(j)] = in[slot brv(((2j+1)k mod 2N) >> 1)].  Through the half-wave's LDS region
@@ -1100,11 +1042,6 @@ constexpr InvPlanWW inv_plan_ww_t(int T0, int T1) {
     for (int r = 0; r < 8; ++r) p.cost += p.fin[r] + 1;
     return p;
 }
-constexpr int kPlanT[8] = {10, 15, 20, 30, 40, 60, 80, 1 << 20};  // candidate thresholds (the last: none)
-#ifndef FHE_PLAN_T
-#define FHE_PLAN_T 1  // 0: no reductions before the transposes (the round-4 plans)
-#endif
-constexpr int kPlanTN = FHE_PLAN_T ? 8 : 0;
 template <int BIN, int LIM>
 constexpr InvPlanWW make_inv_plan_ww() {
     InvPlanWW best = inv_plan_ww_t<BIN, LIM>(kPlanT[7], kPlanT[7]);
@@ -1915,22 +1852,6 @@ FHE_DEV void fwd_wave_s(uint32_t (&v)[NP][16], uint32_t* t, int L, const uint32_
     }
 }
 
-// SignedDigitDecompose (rgsw-acc.cpp:54-91) for digitsG = ND + 1, as decompose2 with SG: the
-// balanced digits 1..ND of the centred value d are the signed bit fields j g of (d + C) ^ M,
-// C = 2^(g-1) sum_{j <= ND} 2^(jg), M = 2^(g-1) sum_{1 <= j <= ND} 2^(jg) (needs (ND + 1) g <= 32 and
-// C + Q < 2^32; Engine checks both)
-struct DecN {
-    uint32_t Qh, C, CmQ, g, M;
-};
-FHE_DEV DecN make_decn(uint32_t Q, uint32_t g, int nd) {
-    const uint32_t h = 1u << (g - 1);
-    uint32_t C = h, M = 0;
-    for (int j = 1; j <= nd; ++j) {
-        C += h << (j * g);
-        M |= h << (j * g);
-    }
-    return DecN{Q >> 1, C, C - Q, g, M};
-}
 // accumulator I/O of the split kernels' seam instantiations: wave c holds component c in layout C, lane L
 // register r <-> EVAL slot ((r >> 2) << 8) | (L << 2) | (r & 3); conventions as acc_load / acc_store
 FHE_DEV uint32_t slot_c(int L, int r) { return ((uint32_t)(r >> 2) << 8) | ((uint32_t)L << 2) | (uint32_t)(r & 3); }
@@ -1950,13 +1871,6 @@ FHE_DEV void acc_store_c(const uint32_t (&acc)[16], const GateArgs& g, uint32_t 
     }
 }
 
-template <int ND, int R>
-FHE_DEV void decompose_n(uint32_t x, const DecN& c, uint32_t (&d)[ND][R], int r) {
-    const uint32_t u = x >= c.Qh ? x + c.CmQ : x + c.C;  // d + C, d = x or x - Q
-    const int32_t w  = (int32_t)(u ^ c.M);
-#pragma unroll
-    for (int j = 0; j < ND; ++j) d[j][r] = (uint32_t)__builtin_amdgcn_sbfe(w, (j + 1) * c.g, c.g);
-}
 }  // namespace
 
 // MF: ciphertext modulus 2N (q = 2N sets: STD128_4, LPF_STD128, LPF_STD128Q): any exponent, the
@@ -2219,6 +2133,9 @@ namespace {
 #endif
 #ifndef FHE_X_ABL
 #define FHE_X_ABL 0     // timing-only ablations (wrong results): 1 no barrier, 2 no key loads
+#endif
+#if FHE_X_ABL && !defined(FHE_ALLOW_WRONG_RESULTS)
+#error "FHE_X_ABL builds a k_blind_rotate_ginx2x that computes wrong ciphertexts (timing-only ablation); add -DFHE_ALLOW_WRONG_RESULTS to build it anyway"
 #endif
 #if FHE_X_ABL == 2
 #define XKEY(p, o) make_uint4((uint32_t)(o), (uint32_t)(o) ^ 5u, (uint32_t)(o) + 3u, (uint32_t)(size_t)(p))
@@ -3304,839 +3221,6 @@ hipError_t launch_blind_rotate_lmk4x(const GateArgs& g, const BootTables& t, con
     return hipGetLastError();
 }
 
-// ===========================================================================
-// K1w: GINX at N = 2048 with the accumulator in registers (k_blind_rotate_n2k<ND, ACCIO>) for the
-// Q < 2^27 rows with even monomial exponents (ciphertext modulus q < 2N): STD256Q (digitsG = 4,
-// ND = 3 retained digits), which otherwise run the one-gate-per-workgroup accumulator K5
-// (bootstrap_wide.hip) with every butterfly through LDS.  As K1s, wave c of a gate owns RLWE
-// component c, here as 32 registers x 64 lanes, through the three layouts (x: 11-bit coefficient
-// or EVAL slot index)
-//   A: lane = x5..x0, register = x10..x6      (COEF; forward stages on bits 10..6, uniform twiddles)
-//   B: lane = (x10..x6) << 1 | x0, register = x5..x1   (stages on bits 5..1, per-lane twiddles)
-//   C: lane = x6..x1, register = (x10..x7) << 1 | x0   (EVAL; the stage on bit 0)
-// with one LDS tile per wave (word of x: x + 2 (x >> 6): A and B conflict-free, C moved as 8-byte
-// pairs).  Per index i (AddToAccCGGI, rgsw-acc-cggi.cpp:102-151): wave c inverse-transforms acc_c
-// (signed, its own reduction plan), decomposes it into its ND digits (SignedDigitDecompose,
-// rgsw-acc.cpp:54-91; rows 2j + c of the RGSW keys) and forward-transforms them; it then multiplies
-// its own digits by the key columns of BOTH components: the sum for its own component stays in its
-// registers, the other one is reduced to a word per slot and handed to the partner through this
-// wave's tile (8 KiB instead of the ND digit polynomials: four gates per CU fit in LDS), and after
-// one barrier each wave adds the partner's word.  acc_c <- acc_c + S+_c (X^a - 1) + S-_c (X^-a - 1)
-// exactly as in K1s; only the order of the modular additions differs.
-// Keys (Engine::pack_n2k, u32 Montgomery with N^-1 folded in), per index and wave c:
-//   [c][q < 2 ND][k2 < 16][64 lanes] uint4 = (K+[r], K+[r + 1], K-[r], K-[r + 1]), r = 2 k2, slot
-//   x(L, r) of layout C; q = 2 j + o: digit row 2 j + c, column c (o = 0) or 1 - c (o = 1).
-// Bounds (Q < 2^27): digits |d| <= 2^(g-1) grow to < 11 Q + 2^(g-1) in the forward transform;
-// |S+-| < ND (11 Q + 2^(g-1)) Q; each reduced sum < 2.6 Q; acc < 5.3 Q after the exchange (the
-// inverse plan's BIN).
-// ===========================================================================
-namespace {
-#ifndef FHE_N2K_OPAQUE
-#define FHE_N2K_OPAQUE 0
-#endif
-#ifndef FHE_N2K_KPF
-#define FHE_N2K_KPF 1   // key chunks requested ahead of their MAC (0: on use)
-#endif
-constexpr int kW2Gates = 2;               // gates per workgroup (2 waves each)
-constexpr int kW2Tile  = 2048 + 64;       // words of one wave's tile
-constexpr int kW2Mono  = 2048 + 1 + 64;   // (plain, Montgomery) pairs psi^(2f) - 1, f in [0, 2048], entry f + (f >> 5)
-constexpr int kW2AccBound = 53;           // |acc| < 5.3 Q between indices (units of Q/10)
-constexpr size_t w2_lds() { return (size_t)(2048 + 2048 + 2 * kW2Mono + 2 * kW2Gates * kW2Tile) * 4; }
-// LDS word of x: x + 2 (x >> 6) (wa2k / wb2k / wc2k below)
-FHE_DEV uint32_t slot_2k(int L, int r) {
-    return ((uint32_t)(r >> 1) << 7) | ((uint32_t)L << 1) | (uint32_t)(r & 1);
-}
-
-// signed forward NTT, layout A (|v| < B) -> C (|v| < B + 11 Q), NP polynomials through one tile
-// (transposed one after the other); twA: Table[0..31] (uniform), s_tab: Table[0..2047] in LDS
-// word of x in each layout as a per-lane base plus a per-register constant (so that every LDS access
-// is base + immediate): A x = (r << 6) | L -> L + 66 r; B x = (G << 6) | (r << 1) | j -> 66 G + j + 2 r;
-// C pair x = (rh << 7) | (L << 1) -> 2 L + 2 (L >> 5) + 132 rh
-FHE_DEV int wa2k(int L) { return L; }
-FHE_DEV int wb2k(int L) { return 66 * (L >> 1) + (L & 1); }
-FHE_DEV int wc2k(int L) { return 2 * L + 2 * (L >> 5); }
-
-// QM, the modulus class: 0: Q < 2^27 (16Q of signed headroom), no reduction; 1: Q < 2^28 (8Q): one signed
-// Montgomery product by 2^32 mod Q after the five A stages (|v| < 5Q + 2^(g-1) -> < 0.82 Q), the six
-// stages after it end below 6.82 Q; 2: Q < 2^29 (4Q): one after stages 3, 6 and 9 (< 3Q + 2^(g-1) ->
-// < 0.875 Q, < 3.875 Q -> < 0.98 Q, < 3.98 Q -> < Q), the last two end below 3 Q
-template <int NP>
-FHE_DEV void red_2k(uint32_t (&v)[NP][32], const Mod& m) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int r = 0; r < 32; ++r) v[p][r] = smont_mul(v[p][r], m.oneR, m);
-}
-
-// one radix-2 stage over the 32 registers: A stages (b = 10..6) pair register bits b - 6 with the twiddles
-// of twA; B stages (b = 5..1) pair register bits b - 1 with s_tab's, indexed by the lane pair G
-template <int NP, bool B>
-FHE_DEV void fwd_2k_stage(uint32_t (&v)[NP][32], int b, int G, const uint32_t* __restrict__ tw, const Mod& m) {
-    const int rb = B ? b - 1 : b - 6;
-#pragma unroll
-    for (int r = 0; r < 32; ++r) {
-        if (r & (1 << rb)) continue;
-        const uint32_t w = B ? tw[(1 << (10 - b)) + (G << (5 - b)) + (r >> b)] : tw[(1 << (10 - b)) + (r >> (rb + 1))];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) ct_bf_s(v[p][r], v[p][r | (1 << rb)], w, m);
-    }
-}
-
-// v - rint(v / Q) Q in 32-bit registers (|v| < 2^31): the float quotient is off by under 2^-20, so the
-// result is below 0.51 Q; no 64-bit temporaries (FRED: K1w GINX, whose 3-digit form spilled 104 VGPRs with
-// smont_mul's and 30 with this; K1w-LMKCDEY keeps red_2k, measured 6% faster there)
-template <int NP>
-FHE_DEV void red_2k_f(uint32_t (&v)[NP][32], const Mod& m) {
-    const float iq = 1.0f / (float)m.Q;
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const int32_t x = (int32_t)v[p][r];
-            const int32_t q = (int32_t)__builtin_rintf((float)x * iq);
-            v[p][r]         = (uint32_t)(x - q * (int32_t)m.Q);
-        }
-}
-
-template <int NP, int QM = 0, bool FRED = false>
-FHE_DEV void fwd_2k_s(uint32_t (&v)[NP][32], uint32_t* t, int L, const uint32_t* __restrict__ twA,
-                      const uint32_t* s_tab, const Mod& m) {
-    // the stages are written out: a loop over them with the reductions inside was left rolled for NP = 3,
-    // and a plain one for NP = 4 (the digit array in scratch)
-    const int G = L >> 1;
-    uint32_t* ta = t + wa2k(L);
-    uint32_t* tb = t + wb2k(L);
-    uint32_t* tc = t + wc2k(L);
-    fwd_2k_stage<NP, false>(v, 10, G, twA, m);
-    fwd_2k_stage<NP, false>(v, 9, G, twA, m);
-    fwd_2k_stage<NP, false>(v, 8, G, twA, m);
-    if (QM == 2 && !FHE_FWD_TIGHT) FRED ? red_2k_f<NP>(v, m) : red_2k<NP>(v, m);  // after stage 3
-    fwd_2k_stage<NP, false>(v, 7, G, twA, m);
-    fwd_2k_stage<NP, false>(v, 6, G, twA, m);
-    if (QM == 1 && !FHE_FWD_TIGHT) red_2k<NP>(v, m);
-    if (QM == 2 && FHE_FWD_TIGHT) FRED ? red_2k_f<NP>(v, m) : red_2k<NP>(v, m);  // after stage 5
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {  // A -> B
-#pragma unroll
-        for (int r = 0; r < 32; ++r) ta[66 * r] = v[p][r];
-        wave_lds_sync();
-#pragma unroll
-        for (int r = 0; r < 32; ++r) v[p][r] = tb[2 * r];
-        wave_lds_sync();
-    }
-    fwd_2k_stage<NP, true>(v, 5, G, s_tab, m);
-    if (QM == 2 && !FHE_FWD_TIGHT) FRED ? red_2k_f<NP>(v, m) : red_2k<NP>(v, m);  // after stage 6
-    fwd_2k_stage<NP, true>(v, 4, G, s_tab, m);
-    fwd_2k_stage<NP, true>(v, 3, G, s_tab, m);
-    fwd_2k_stage<NP, true>(v, 2, G, s_tab, m);
-    if (QM == 2) FRED ? red_2k_f<NP>(v, m) : red_2k<NP>(v, m);  // after stage 9
-    fwd_2k_stage<NP, true>(v, 1, G, s_tab, m);
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {  // B -> C
-#pragma unroll
-        for (int r = 0; r < 32; ++r) tb[2 * r] = v[p][r];
-        wave_lds_sync();
-#pragma unroll
-        for (int rh = 0; rh < 16; ++rh) {
-            const uint2 q = *reinterpret_cast<const uint2*>(tc + 132 * rh);
-            v[p][2 * rh]     = q.x;
-            v[p][2 * rh + 1] = q.y;
-        }
-        wave_lds_sync();
-    }
-#pragma unroll
-    for (int rh = 0; rh < 16; ++rh) {
-        const uint32_t w = s_tab[1024 + (rh << 6) + L];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) ct_bf_s(v[p][2 * rh], v[p][2 * rh + 1], w, m);
-    }
-}
-
-// the signed inverse's reduction plan (as InvPlanS / make_inv_plan_ww): stage st = 0 (C, register bit
-// 0), 1..5 (B, register bits 0..4), 6..9 (A, register bits 0..3), 10 (the last, register bit 4); a
-// transpose precedes stages 1 and 6
-struct InvPlan2k {
-    bool red[11][32];
-    bool redT[2][32];  // before the C -> B / B -> A transpose (as InvPlanWW)
-    int fin[16];
-    int cost;
-};
-template <int BIN, int LIM>
-constexpr InvPlan2k inv_plan_2k_t(int T0, int T1) {
-    InvPlan2k p{};
-    int B[32] = {};
-    for (int r = 0; r < 32; ++r) B[r] = BIN;
-    const int bits[11] = {0, 0, 1, 2, 3, 4, 0, 1, 2, 3, 4};
-    int nred = 0;
-    for (int st = 0; st < 11; ++st) {
-        if (st == 1 || st == 6) {
-            const int k = st == 1 ? 0 : 1, T = k ? T1 : T0;
-            int U = 0;
-            for (int r = 0; r < 32; ++r) {
-                if (B[r] > T) {
-                    B[r]         = 10;
-                    p.redT[k][r] = true;
-                    ++nred;
-                }
-                U = B[r] > U ? B[r] : U;
-            }
-            for (int r = 0; r < 32; ++r) B[r] = U;
-        }
-        const int bt = bits[st];
-        for (int r = 0; r < 32; ++r) {
-            if (r & (1 << bt)) continue;
-            const int q = r | (1 << bt);
-            while (B[r] + B[q] > LIM) {
-                const int e = B[r] >= B[q] ? r : q;
-                B[e]        = 10;
-                p.red[st][e] = true;
-                ++nred;
-            }
-            if (st == 10) {
-                int f = 0;
-                while ((10 << f) < B[r] + B[q]) ++f;
-                p.fin[r] = f;
-            }
-            B[r] = B[r] + B[q];
-            B[q] = 10;
-        }
-    }
-    p.cost = 2 * nred;
-    for (int r = 0; r < 16; ++r) p.cost += p.fin[r] + 1;
-    return p;
-}
-template <int BIN, int LIM>
-constexpr InvPlan2k make_inv_plan_2k() {
-    InvPlan2k best = inv_plan_2k_t<BIN, LIM>(kPlanT[7], kPlanT[7]);
-    for (int a = 0; a < kPlanTN; ++a)
-        for (int b = 0; b < kPlanTN; ++b) {
-            const InvPlan2k p = inv_plan_2k_t<BIN, LIM>(kPlanT[a], kPlanT[b]);
-            if (p.cost < best.cost) best = p;
-        }
-    return best;
-}
-// signed inverse NTT, layout C (EVAL, |v| < BIN Q / 10) -> A (COEF), canonical [0, Q); the keys carry
-// N^-1, so the last stage scales by TableI[1] only (w1R)
-// LIM: the signed headroom in units of Q/10 (160: Q < 2^27; 80: Q < 2^28, where the last stage's
-// x + y + (Q << fin) stays below 16 Q < 2^32)
-template <int BIN, int LIM = 160>
-FHE_DEV void inv_2k_s(uint32_t (&v)[32], uint32_t* t, int L, const uint32_t* __restrict__ twAi,
-                      const uint32_t* s_tabI, uint32_t w1R, uint32_t oneR, const Mod& m) {
-    constexpr InvPlan2k P = make_inv_plan_2k<BIN, LIM>();
-    auto redp = [&](int st) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r)
-            if (P.red[st][r]) v[r] = smont_mul(v[r], oneR, m);
-    };
-    auto redt = [&](int k) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r)
-            if (P.redT[k][r]) v[r] = smont_mul(v[r], oneR, m);
-    };
-    auto gs = [&](uint32_t& x, uint32_t& y, uint32_t w) {
-        const uint32_t s = x + y;
-        y                = smont_mul(x - y, w, m);
-        x                = s;
-    };
-    const int G = L >> 1;
-    uint32_t* ta = t + wa2k(L);
-    uint32_t* tb = t + wb2k(L);
-    uint32_t* tc = t + wc2k(L);
-    redp(0);
-#pragma unroll
-    for (int rh = 0; rh < 16; ++rh) gs(v[2 * rh], v[2 * rh + 1], s_tabI[1024 + (rh << 6) + L]);
-    // C -> B
-    redt(0);
-#pragma unroll
-    for (int rh = 0; rh < 16; ++rh)
-        *reinterpret_cast<uint2*>(tc + 132 * rh) = make_uint2(v[2 * rh], v[2 * rh + 1]);
-    wave_lds_sync();
-#pragma unroll
-    for (int r = 0; r < 32; ++r) v[r] = tb[2 * r];
-    wave_lds_sync();
-#pragma unroll
-    for (int b = 1; b <= 5; ++b) {
-        const int rb = b - 1;
-        redp(b);
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], s_tabI[(1 << (10 - b)) + (G << (5 - b)) + (r >> b)]);
-        }
-    }
-    // B -> A
-    redt(1);
-#pragma unroll
-    for (int r = 0; r < 32; ++r) tb[2 * r] = v[r];
-    wave_lds_sync();
-#pragma unroll
-    for (int r = 0; r < 32; ++r) v[r] = ta[66 * r];
-    wave_lds_sync();
-#pragma unroll
-    for (int b = 6; b <= 9; ++b) {
-        const int rb = b - 6;
-        redp(b);
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], twAi[(1 << (10 - b)) + (r >> (rb + 1))]);
-        }
-    }
-    // bit 10 (transformnat-impl.h:599-623), canonical results as inv_pass_s
-    redp(10);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const uint32_t x = v[r], y = v[r | 16];
-        uint32_t s       = x + y + (m.Q << P.fin[r]);
-#pragma unroll
-        for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
-        const uint32_t d = smont_mul(x - y, w1R, m);
-        v[r]             = s;
-        v[r | 16]        = min(d, d + m.Q);
-    }
-}
-}  // namespace
-
-// QM 2 (2^27 <= Q < 2^29, STD256 / STD256_3 with q = 2048): the forward transform reduced three times
-// (fwd_2k_s), the monomial pairs centred to (-Q/2, Q/2] and the product's low word taken signed, so that
-// |acc| < 2.6 Q (own wave: |lo mp.x| 2^-32 < Q/4 per column, |hi mp.y| 2^-32 < 3 ND Q^3 2^-65 < 0.07 Q,
-// |acc oneR| 2^-32 < A/8, + Q/2; the partner's share without the acc term) fits the 4 Q plan
-// FULL (q = 2N, STD256_4: odd monomial exponents): the table holds psi^g - 1 for g in [0, 2048] and
-// psi^(g + 2048) - 1 = -(psi^g - 1) - 2 is formed on the fly, (-x - 2, -y - 2R) with 2R centred (|y'| < Q:
-// |acc| < 2.93 Q, bound 30)
-// QM 3 (round 5): the centred products of QM 2 for Q < 2^27 (STD256Q_3 / STD256Q_4: q = 2N, 4 digits), with QM 0's
-// unreduced forward transform and 16 Q inverse plan: |D| < 11 Q + 2^(g-1), |S+-| < 44 Q^2, so each pair's hi part
-// times a monomial half adds < 0.05 Q; own word < Q/2 (lo parts) + 0.09 Q + A/32 + Q/2, the partner's the same
-// without A: A < 2.25 Q (bound 25)
-template <int ND, int QM, bool FULL>
-constexpr int kW2Bound = QM == 3 ? 25 : QM == 2 ? (FULL ? (ND == 4 ? 32 : 30) : 27) : kW2AccBound;
-#ifndef FHE_N2K_QM3
-#define FHE_N2K_QM3 1  // 4-digit K1w GINX at Q < 2^27 in the QM 3 class (0: QM 2, the round-4 form)
-#endif
-#ifndef FHE_N2K_ONEWAVE
-#define FHE_N2K_ONEWAVE 0  // bit 0 / 1: the 4- / 3-digit K1w GINX forms at one wave per SIMD (512 registers)
-#endif
-template <int ND, bool ACCIO, int QM = 0, bool FULL = false>
-__global__ void __launch_bounds__(128 * kW2Gates,
-                                  (((FHE_N2K_ONEWAVE & 1) && ND == 4) || ((FHE_N2K_ONEWAVE & 2) && ND == 3)) ? 1 : 2)
-    k_blind_rotate_n2k(GateArgs g, BootTables T, const uint4* __restrict__ keys, const uint16_t* __restrict__ idx,
-                       const uint32_t* __restrict__ tvb, uint64_t* __restrict__ ext_a, uint64_t* __restrict__ ext_b,
-                       const uint32_t* __restrict__ twAf, const uint32_t* __restrict__ twAi) {
-    constexpr int kQ = 2 * ND;  // key vectors per slot pair: ND digit rows x 2 columns
-    static_assert(!FULL || QM >= 2, "the full-resolution monomials need the centred (QM 2 / 3) products");
-    constexpr int BIN = kW2Bound<ND, QM, FULL>, LIM = QM == 2 ? 40 : 160;
-    constexpr int QF = QM == 3 ? 0 : QM;  // the forward transform's reduction class
-    constexpr bool CEN = QM >= 2;         // centred monomial pairs and signed lo halves
-    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-    uint32_t* s_tab  = sm;
-    uint32_t* s_tabI = sm + 2048;
-    uint2* s_mono2   = reinterpret_cast<uint2*>(sm + 4096);
-    uint32_t* s_tile = sm + 4096 + 2 * kW2Mono;
-    for (int i = threadIdx.x; i < 2048; i += blockDim.x) {
-        s_tab[i]  = T.tabF[i];
-        s_tabI[i] = T.tabI[i];
-    }
-    for (int i = threadIdx.x; i < kW2Mono; i += blockDim.x) {
-        uint32_t mx = T.monoP[i], my = T.mono[i];
-        if (CEN) {  // centred: (-Q/2, Q/2]
-            mx = mx > T.Q / 2 ? mx - T.Q : mx;
-            my = my > T.Q / 2 ? my - T.Q : my;
-        }
-        s_mono2[i] = make_uint2(mx, my);
-    }
-
-    const int wave = threadIdx.x >> 6, L = threadIdx.x & 63;
-    const int c = wave & 1;  // RLWE component of this wave
-    const uint32_t gslot = blockIdx.x * kW2Gates + (wave >> 1);
-    const bool live = gslot < g.count;
-    const uint32_t gate = live ? gslot : g.count - 1;  // spare waves shadow the last gate: every wave meets every barrier
-    uint32_t* tile    = s_tile + wave * kW2Tile;
-    uint32_t* partner = s_tile + (wave ^ 1) * kW2Tile;
-    const Mod m0 = make_mod(T);
-    const Mod& m = m0;
-    __syncthreads();
-
-    // initial accumulator (BootstrapGateCore, binfhe-base-scheme.cpp:556-575): acc1 = NTT(m), acc0 = 0
-    uint32_t acc[32];
-    if (ACCIO && !g.acc_tv) {
-        const uint64_t* src = g.acc_io + ((size_t)gate * 2 + c) * g.N;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = csub(mont_mul((uint32_t)src[slot_2k(L, r)], T.ninvR, m), m.Q);
-    } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        uint32_t tv[1][32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const uint32_t x = ((uint32_t)r << 6) | (uint32_t)L;
-            uint32_t v       = 0;
-            if (x % g.factor == 0) {
-                const uint32_t bx = (b - x / g.factor) & cm;
-                v                 = (bx >= g.lb && bx < g.ub) ? g.lv : g.uv;
-            }
-            tv[0][r] = v;
-        }
-        fwd_2k_s<1, QF, true>(tv, tile, L, twAf, s_tab, m);
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = smont_mul(tv[0][r], T.ninvR, m);  // (-Q, Q), N^-1 scaled
-    } else {
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = 0;
-    }
-
-    const uint16_t* gidx = idx + (size_t)gate * g.n;
-    const DecN dec       = make_decn(m.Q, g.gbits, ND);
-    // monomial of slot x(L, r): e = m (2 brv11(x) + 1) mod 2N, m = a 2N / ctmod even, in half units
-    // f = e / 2 = as (32 brv6(L) + 1) + as 2 brv4(r >> 1) mod 2048 (bit 0 of x adds as 2048 = 0)
-    // FULL: e = a (32 brv6(L) + 1) + a 2 brv4(r >> 1) + a 2048 (r & 1) mod 4096
-    const uint32_t lmul = 32 * (__builtin_bitreverse32((uint32_t)L) >> 26) + 1;
-    const uint4* kc     = keys + (size_t)c * (kQ * 16 * 64) + L;
-    uint32_t two_r = 0;
-    if (FULL) {
-        two_r = 2 * T.oneR;
-        two_r = two_r >= T.Q ? two_r - T.Q : two_r;
-        two_r = two_r > T.Q / 2 ? two_r - T.Q : two_r;
-    }
-    // u or -u - (2, 2R) by a mask (0 or ~0): no control flow around the MAC
-    auto negp = [&](uint2 u, uint32_t sm) {
-        return make_uint2(((u.x ^ sm) - sm) - (2u & sm), ((u.y ^ sm) - sm) - (two_r & sm));
-    };
-    for (uint32_t i = 0; i < g.n; ++i) {
-        const Mod m       = fresh_nq(m0);
-        const uint32_t as = __builtin_amdgcn_readfirstlane((uint32_t)gidx[i]) >> (FULL ? 0 : 1);
-        const uint4* kb   = kc + (size_t)i * (2 * kQ * 16 * 64);
-        // the uniform twiddles re-read per index (hoisted, the 62 of them would sit in VGPRs across the loop)
-        const uint32_t* twF = twAf;
-        const uint32_t* twI = twAi;
-        asm volatile("" : "+s"(twF), "+s"(twI));
-#if FHE_N2K_OPAQUE
-        // the lane index and this wave's tiles opaque per index: the per-lane LDS bases are re-derived
-        // inside the body instead of being kept (spilled) across the loop
-        int L_o = L;
-        uint32_t *tile_o = tile, *partner_o = partner;
-        asm volatile("" : "+v"(L_o), "+v"(tile_o), "+v"(partner_o));
-        const int L = L_o;
-        uint32_t* const tile    = tile_o;
-        uint32_t* const partner = partner_o;
-#endif
-        constexpr int KB = ND == 4 ? 1 : FHE_N2K_KPF + 1;  // 4 digits: no registers for the key ring
-        uint4 kq[KB][kQ];
-        __syncthreads();  // the partner has read this wave's tile (previous index)
-        uint32_t d[ND][32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) d[0][r] = acc[r];
-        inv_2k_s<BIN, LIM>(d[0], tile, L, twI, s_tabI, T.w1R, m.oneR, m);
-#pragma unroll
-        for (int r = 0; r < 32; ++r) decompose_n<ND>(d[0][r], dec, d, r);
-        fwd_2k_s<ND, QF, true>(d, tile, L, twF, s_tab, m);
-        constexpr uint32_t EM = FULL ? 4095u : 2047u;
-        const uint32_t fl = (as * lmul) & EM;
-#pragma unroll
-        for (int q = 0; q < kQ; ++q) kq[0][q] = kb[(q * 16 + 0) * 64];
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) {
-            if (KB == 2 && k2 + 1 < 16) {
-#pragma unroll
-                for (int q = 0; q < kQ; ++q) kq[(k2 + 1) % KB][q] = kb[(q * 16 + k2 + 1) * 64];
-            } else if (KB == 1 && k2 > 0) {
-#pragma unroll
-                for (int q = 0; q < kQ; ++q) kq[0][q] = kb[(q * 16 + k2) * 64];
-            }
-            asm volatile("" ::: "memory");
-            const uint32_t ur = __builtin_amdgcn_readfirstlane(
-                (as * 2u * (__builtin_bitreverse32((uint32_t)k2) >> 28)) & EM);
-            uint2 mp, mn;
-            if (FULL) {
-                const uint32_t e0 = (fl + ur) & 4095u, en = (4096u - e0) & 4095u;
-                const uint32_t g0 = e0 & 2047u, gn = en & 2047u;
-                const uint2 t0 = s_mono2[g0 + (g0 >> 5)], tn = s_mono2[gn + (gn >> 5)];
-                mp = negp(t0, 0u - ((e0 >> 11) & 1u));
-                mn = negp(tn, 0u - ((en >> 11) & 1u));
-            } else {
-                const uint32_t f = (fl + ur) & 2047u, fn = 2048u - f;
-                mp = s_mono2[f + (f >> 5)];
-                mn = s_mono2[fn + (fn >> 5)];
-            }
-            const uint4* q4 = kq[k2 % KB];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int r = 2 * k2 + e;
-                if (FULL && e == 1) {  // odd a: slot r + 1 is 2048 a further
-                    mp = negp(mp, 0u - (as & 1u));
-                    mn = negp(mn, 0u - (as & 1u));
-                }
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {  // o = 0: this wave's component, 1: the partner's
-                    int64_t S1 = 0, S2 = 0;
-#pragma unroll
-                    for (int j = 0; j < ND; ++j) {
-                        const uint4 kv = q4[2 * j + o];
-                        S1 += (int64_t)(int32_t)d[j][r] * (int32_t)(e ? kv.y : kv.x);
-                        S2 += (int64_t)(int32_t)d[j][r] * (int32_t)(e ? kv.w : kv.z);
-                    }
-                    int64_t S;
-                    if (CEN) {  // S1 = hi 2^32 + lo with lo signed
-                        const int32_t l1 = (int32_t)S1, l2 = (int32_t)S2;
-                        const int32_t h1 = (int32_t)((S1 - l1) >> 32), h2 = (int32_t)((S2 - l2) >> 32);
-                        S = (int64_t)l1 * (int32_t)mp.x + (int64_t)h1 * (int32_t)mp.y;
-                        S += (int64_t)l2 * (int32_t)mn.x + (int64_t)h2 * (int32_t)mn.y;
-                    } else {
-                        S = (int64_t)((uint64_t)(uint32_t)S1 * mp.x) + (int64_t)(int32_t)(S1 >> 32) * (int32_t)mp.y;
-                        S += (int64_t)((uint64_t)(uint32_t)S2 * mn.x) + (int64_t)(int32_t)(S2 >> 32) * (int32_t)mn.y;
-                    }
-                    if (o == 0) {
-                        S += (int64_t)(int32_t)acc[r] * (int32_t)T.oneR;
-                        acc[r] = smont_red(S, m);
-                    } else {
-                        tile[(r << 6) | L] = smont_red(S, m);
-                    }
-                }
-            }
-        }
-        __syncthreads();  // both waves' partner words are in LDS
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] += partner[(r << 6) | L];
-    }
-
-    if (ACCIO) {  // every wave of the workgroup leaves here: no barrier is skipped by some only
-        if (live) {
-            uint64_t* dst = g.acc_io + ((size_t)gate * 2 + c) * g.N;
-#pragma unroll
-            for (int r = 0; r < 32; ++r) {
-                const int32_t v = (int32_t)smont_mul(acc[r], T.nR, m);
-                dst[slot_2k(L, r)] = (uint64_t)(uint32_t)(v < 0 ? v + (int32_t)m.Q : v);
-            }
-        }
-        return;
-    }
-    // extraction (binfhe-base-scheme.cpp:110-121): canonical COEF in layout A; wave 0 writes the
-    // transposed acc0 (coefficient k -> position N - k, negated), wave 1 the b term from acc1[0]
-    __syncthreads();  // the partner has read this wave's tile
-    inv_2k_s<BIN, LIM>(acc, tile, L, twAi, s_tabI, T.w1R, m.oneR, m);
-    if (!live) return;
-    if (c == 0) {
-        uint64_t* oa = ext_a + (size_t)gate * g.N;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const uint32_t x = ((uint32_t)r << 6) | (uint32_t)L;
-            const uint32_t v = acc[r];
-            const uint32_t o = (x == 0 || v == 0) ? v : m.Q - v;
-            oa[(g.N - x) & (g.N - 1)] = g.msb_out ? mod_switch(o, m.Q, g.qKS) : o;
-        }
-    } else if (L == 0) {
-        const uint32_t bb = add_mod(g.b_const, acc[0], m.Q);
-        ext_b[gate]       = g.msb_out ? mod_switch(bb, m.Q, g.qKS) : bb;
-    }
-}
-
-bool n2k_supported(const GateArgs& g, const BootTables& t, int nd) {
-    // The monomial table is full-resolution (psi^g - 1, the kernel negating past psi^2048) exactly when the set's
-    // q = 2N, half-resolution (psi^(2f) - 1) otherwise (Engine::build_tables_n2k).  The full-resolution
-    // instantiations (3 retained digits at 2^27 <= Q < 2^29, 4 digits) take any ciphertext modulus <= 2N; the
-    // half-resolution ones need even exponents, ciphertext moduli below 2N (a seam call at 2N stays on K5).
-    // 3 retained digits at Q < 2^29 (Q >= 2^27: QM 2), 2 retained digits at 2^27 <= Q < 2^29.
-    const bool full = g.q == 2 * g.N;
-    const bool qok = full ? (nd == 4 || (nd == 3 && t.Q >= (1u << 27))) : g.ctmod < 2 * g.N;
-    const bool ndok = nd == 3 || (nd == 2 && t.Q >= (1u << 27)) || (nd == 4 && full);
-    return t.Q < (1u << 29) && ndok && g.N == 2048 && qok && g.ctmod <= 2 * g.N &&
-           g.tv == nullptr && g.tv64 == nullptr && g.gbits >= 2 && (uint32_t)(nd + 1) * g.gbits <= 32;
-}
-
-hipError_t launch_blind_rotate_n2k(const GateArgs& g, const BootTables& t, const void* keys, const uint16_t* idx,
-                                   const uint32_t* tvb, uint64_t* ext_a, uint64_t* ext_b, int nd, hipStream_t s) {
-    if (g.count == 0) return hipSuccess;
-    if (!n2k_supported(g, t, nd)) return hipErrorInvalidValue;
-    static const bool attr = [] {
-        for (const void* k : {reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, false>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, false, 2>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, true, 2>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<2, false, 2>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<2, true, 2>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, false, 2, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<3, true, 2, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<4, false, 2, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<4, true, 2, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<4, false, 3, true>),
-                              reinterpret_cast<const void*>(&k_blind_rotate_n2k<4, true, 3, true>)})
-            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w2_lds());
-        return true;
-    }();
-    (void)attr;
-    const uint32_t blocks = (g.count + kW2Gates - 1) / kW2Gates;
-    const uint4* k = static_cast<const uint4*>(keys);
-#define FHE_N2K(ND_, IO, QM_, ...)                                                                                 \
-    hipLaunchKernelGGL((k_blind_rotate_n2k<ND_, IO, QM_, ##__VA_ARGS__>), dim3(blocks), dim3(128 * kW2Gates), w2_lds(), \
-                       s, g, t, k, idx, tvb, ext_a, ext_b, t.twA_fwd, t.twA_inv)
-    if (g.q == 2 * g.N) {  // full-resolution table: STD256_4 (29-bit Q, q = 2N); STD256Q_3 / STD256Q_4 (4 digits)
-        if (nd == 4 && FHE_N2K_QM3 && t.Q < (1u << 27)) {  // STD256Q_3 / STD256Q_4: no forward reductions (QM 3)
-            if (g.acc_io) FHE_N2K(4, true, 3, true); else FHE_N2K(4, false, 3, true);
-        } else if (nd == 4) { if (g.acc_io) FHE_N2K(4, true, 2, true); else FHE_N2K(4, false, 2, true); }
-        else if (g.acc_io) FHE_N2K(3, true, 2, true); else FHE_N2K(3, false, 2, true);
-    } else if (t.Q < (1u << 27)) {  // STD256Q
-        if (g.acc_io) FHE_N2K(3, true, 0); else FHE_N2K(3, false, 0);
-    } else if (nd == 3) {  // STD256_3 (29-bit Q)
-        if (g.acc_io) FHE_N2K(3, true, 2); else FHE_N2K(3, false, 2);
-    } else {  // STD256 (29-bit Q, digitsG 3)
-        if (g.acc_io) FHE_N2K(2, true, 2); else FHE_N2K(2, false, 2);
-    }
-#undef FHE_N2K
-    return hipGetLastError();
-}
-
-// ===========================================================================
-// K1w for LMKCDEY: k_blind_rotate_lmk2k<ACCIO> (RingGSWAccumulatorLMKCDEY::EvalAcc,
-// rgsw-acc-lmkcdey.cpp:70-287) at N = 2048, Q < 2^27, digitsG = 4 (ND = 3 retained digits):
-// STD256Q_LMKCDEY and STD256Q_3_LMKCDEY, which otherwise run K5's op-list form.  One gate per
-// 128-thread workgroup (op lists differ per gate, so a barrier may only join the two waves of one
-// gate); wave c owns component c in K1w's layout C.  Per op of k_prep_lmk_w's list:
-//   EXT(i)  (AddToAccLMKCDEY, :228-254): each wave inverse-transforms its component, decomposes it into
-//           its 3 digits (rows 2 j + c) and forward-transforms them, then multiplies them by both key
-//           columns: the sum for its own component replaces acc_c, the other one is reduced to a word
-//           per slot and handed over through this wave's tile (as K1w's GINX exchange).
-//   AUTO(t) (Automorphism, :257-287): both components permuted in EVAL through the wave's tile; wave 0
-//           inverse-transforms acc0', decomposes and forward-transforms it, acc0 <- sum_d D_d ak[t][d][0]
-//           and hands sum_d D_d ak[t][d][1] to wave 1, which adds it to acc1'.
-// Keys (Engine::pack_n2k, u32 Montgomery with N^-1 folded in), one uint4 = 4 consecutive registers:
-//   ek: [i][c][q < 6][k4 < 8][64 lanes], q = 2 j + o: digit row 2 j + c, column c (o = 0) or 1 - c (o = 1);
-//   ak: [t][q < 6][k4 < 8][64 lanes], q = 2 d + col.
-// Bounds (Q < 2^27): |D| < 11 Q + 2^(g-1) after the forward transform, |S| < 3 (11 Q + 2^6) Q < 2^59,
-// each reduced sum < 1.6 Q, acc < 3.2 Q after an exchange (the inverse plan's BIN = 33).
-// ===========================================================================
-namespace {
-// |acc| between ops, units of Q/10: 2 (ND (11 Q + 2^(g-1)) Q 2^-32 + Q/2) for Q < 2^27; Q28 (ND = 2,
-// 2^27 <= Q < 2^28, the forward transform reduced once): 2 (2 (6.82 Q) Q 2^-32 + Q/2) < 2.8 Q
-// QM 2 (Q < 2^29, digits below 3 Q after the forward transform): 2 (ND 3 Q Q 2^-32 + Q/2) -> 33 (ND 3)
-// FHE_FWD_TIGHT, Q28: no forward reduction, digits below 7.59 Q (see there): 2 (ND 7.59 Q Q 2^-32 + Q/2) -> 29 / 39
-template <int ND, int QM>
-constexpr int kL2AccBound = QM == 1 ? (FHE_FWD_TIGHT ? (ND == 3 ? 39 : 29) : (ND == 3 ? 36 : 28))
-                                    : QM == 2 ? (ND == 3 ? 33 : 25) : 33;
-constexpr size_t l2k_lds() { return (size_t)(2048 + 2048 + 2 * kW2Tile) * 4; }
-
-// EVAL automorphism X -> X^k on layout C through this wave's tile (as automorphism_c at N = 1024):
-// slot x(L, r) evaluates at psi^(2 brv11(x) + 1), 2 brv11(x) + 1 = 32 brv6(L) + 1 + 2048 (r & 1) +
-// 2 brv4(r >> 1); the value at x moves from the slot y with 2 brv11(y) + 1 = k (2 brv11(x) + 1) mod 4N
-FHE_DEV void automorphism_2k(uint32_t (&v)[32], uint32_t* t, int L, uint32_t k) {
-    uint32_t* tc = t + wc2k(L);
-#pragma unroll
-    for (int rh = 0; rh < 16; ++rh) *reinterpret_cast<uint2*>(tc + 132 * rh) = make_uint2(v[2 * rh], v[2 * rh + 1]);
-    wave_lds_sync();
-    const uint32_t cl = (32u * (__builtin_bitreverse32((uint32_t)L) >> 26) + 1u) * k;
-#pragma unroll
-    for (int r = 0; r < 32; ++r) {
-        const uint32_t sr = (2048u * (uint32_t)(r & 1) + 2u * (__builtin_bitreverse32((uint32_t)(r >> 1)) >> 28)) * k;
-        const uint32_t e  = (cl + sr) & 4095u;                  // odd
-        const uint32_t sx = __builtin_bitreverse32(e >> 1) >> 21;  // source slot brv11((e - 1) / 2)
-        v[r] = t[sx + 2 * (sx >> 6)];
-    }
-    wave_lds_sync();
-}
-
-// acc_c <- (own sum), partner word <- (other sum) over ND digits and the 2 ND key vectors of kb
-// (q = 2 j + o); keys one chunk of 4 registers ahead
-template <int ND>
-FHE_DEV void mac_2k(uint32_t (&acc)[32], const uint32_t (&d)[ND][32], const uint4* kb, uint32_t* tile, int L,
-                    const Mod& m) {
-    constexpr int kQ = 2 * ND;
-    uint4 kq[2][kQ];
-#pragma unroll
-    for (int q = 0; q < kQ; ++q) kq[0][q] = kb[(q * 8 + 0) * 64];
-#pragma unroll
-    for (int k4 = 0; k4 < 8; ++k4) {
-        if (k4 + 1 < 8) {
-#pragma unroll
-            for (int q = 0; q < kQ; ++q) kq[(k4 + 1) & 1][q] = kb[(q * 8 + k4 + 1) * 64];
-        }
-        asm volatile("" ::: "memory");
-        const uint4* q4 = kq[k4 & 1];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * k4 + e;
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-                int64_t S = 0;
-#pragma unroll
-                for (int j = 0; j < ND; ++j) {
-                    const uint4 kv   = q4[2 * j + o];
-                    const uint32_t w = e == 0 ? kv.x : e == 1 ? kv.y : e == 2 ? kv.z : kv.w;
-                    S += (int64_t)(int32_t)d[j][r] * (int32_t)w;
-                }
-                if (o == 0) acc[r] = smont_red(S, m);
-                else tile[(r << 6) | L] = smont_red(S, m);
-            }
-        }
-    }
-}
-}  // namespace
-
-template <int ND, bool ACCIO, int QM = 0>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
-    k_blind_rotate_lmk2k(GateArgs g, BootTables T, const uint4* __restrict__ ek, const uint4* __restrict__ ak,
-                         const uint16_t* __restrict__ ops, const uint32_t* __restrict__ nops, uint32_t maxops,
-                         const uint32_t* __restrict__ tvb, uint64_t* __restrict__ ext_a, uint64_t* __restrict__ ext_b,
-                         const uint32_t* __restrict__ twAf, const uint32_t* __restrict__ twAi) {
-    constexpr int kQ = 2 * ND;
-    constexpr int BIN = kL2AccBound<ND, QM>, LIM = QM == 2 ? 40 : QM == 1 ? 80 : 160;
-    extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-    uint32_t* s_tab  = sm;
-    uint32_t* s_tabI = sm + 2048;
-    uint32_t* s_tile = sm + 4096;
-    for (int i = threadIdx.x; i < 2048; i += blockDim.x) {
-        s_tab[i]  = T.tabF[i];
-        s_tabI[i] = T.tabI[i];
-    }
-    // wave c: RLWE component c.  (Giving component 0's role, the one the AUTO ops load, to the second
-    // wave in half the workgroups was measured 1.7% slower: profiles/r04_lmk2k_swap_ab.txt)
-    const int c = threadIdx.x >> 6, L = threadIdx.x & 63;
-    const uint32_t gate = blockIdx.x;
-    uint32_t* tile    = s_tile + c * kW2Tile;
-    uint32_t* partner = s_tile + (c ^ 1) * kW2Tile;
-    const Mod m0 = make_mod(T);
-    const Mod& m = m0;
-    const uint32_t M = 2 * g.N;
-    __syncthreads();
-
-    // BootstrapGateCore (binfhe-base-scheme.cpp:556-575): acc1 = NTT(m), acc0 = 0; then
-    // acc1 <- acc1(X^(2N-5)) (rgsw-acc-lmkcdey.cpp:99; acc0 = 0 is invariant)
-    uint32_t acc[32];
-    if (ACCIO && !g.acc_tv) {
-        const uint64_t* src = g.acc_io + ((size_t)gate * 2 + c) * g.N;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = csub(mont_mul((uint32_t)src[slot_2k(L, r)], T.ninvR, m), m.Q);
-        if (c == 1) automorphism_2k(acc, tile, L, M - 5);
-    } else if (c == 1) {
-        const uint32_t b = tvb[gate], cm = g.ctmod - 1;
-        uint32_t tv[1][32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const uint32_t x = ((uint32_t)r << 6) | (uint32_t)L;
-            uint32_t v       = 0;
-            if (x % g.factor == 0) {
-                const uint32_t bx = (b - x / g.factor) & cm;
-                v                 = (bx >= g.lb && bx < g.ub) ? g.lv : g.uv;
-            }
-            tv[0][r] = v;
-        }
-        fwd_2k_s<1, QM>(tv, tile, L, twAf, s_tab, m);
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = smont_mul(tv[0][r], T.ninvR, m);  // (-Q, Q), N^-1 scaled
-        automorphism_2k(acc, tile, L, M - 5);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 32; ++r) acc[r] = 0;
-    }
-
-    const DecN dec       = make_decn(m.Q, g.gbits, ND);
-    const uint16_t* gops = ops + (size_t)gate * maxops;
-    const uint32_t cnt   = __builtin_amdgcn_readfirstlane(nops[gate]);
-    for (uint32_t it = 0; it < cnt; ++it) {
-        const Mod m       = fresh_nq(m0);
-        const uint32_t op = __builtin_amdgcn_readfirstlane((uint32_t)gops[it]);
-        const uint32_t* twF = twAf;
-        const uint32_t* twI = twAi;
-        asm volatile("" : "+s"(twF), "+s"(twI));
-        __syncthreads();  // the partner has read this wave's tile (previous op)
-        // ---- AddToAccLMKCDEY (op < 0x8000): acc_c <- sum over both components' digits of D ek[op][row][c];
-        // ---- Automorphism(5^t or 2N - 5, ak[t]) (op = 0x8000 | t): acc0' -> COEF -> digits -> EVAL,
-        // acc0 replaced, acc1's share to the tile.  One copy of the digit path serves both (the two copies
-        // put the digit array of the 3-digit, 29-bit form in scratch)
-        const bool isauto = op & 0x8000u;
-        const uint32_t t  = op & 0x7fffu;
-        if (isauto) {
-            uint32_t kexp = M - 5;
-            if (t) {
-                kexp = 1;
-                for (uint32_t z = 0; z < t; ++z) kexp = (kexp * 5u) & (M - 1);
-            }
-            automorphism_2k(acc, tile, L, kexp);
-        }
-        if (!isauto || c == 0) {
-            uint32_t d[ND][32];
-#pragma unroll
-            for (int r = 0; r < 32; ++r) d[0][r] = acc[r];
-            inv_2k_s<BIN, LIM>(d[0], tile, L, twI, s_tabI, T.w1R, m.oneR, m);
-#pragma unroll
-            for (int r = 0; r < 32; ++r) decompose_n<ND>(d[0][r], dec, d, r);
-            fwd_2k_s<ND, QM>(d, tile, L, twF, s_tab, m);
-            const uint4* key = isauto ? ak + (size_t)t * (kQ * 8 * 64) : ek + ((size_t)op * 2 + c) * (kQ * 8 * 64);
-            mac_2k<ND>(acc, d, key + L, tile, L, m);
-        }
-        __syncthreads();  // the partner words (AddToAcc: both waves'; Automorphism: wave 0's share of acc1)
-        if (!isauto) {
-#pragma unroll
-            for (int r = 0; r < 32; ++r) acc[r] += partner[(r << 6) | L];
-        } else if (c == 1) {
-#pragma unroll
-            for (int r = 0; r < 32; ++r) {
-                const int64_t S = (int64_t)(int32_t)acc[r] * (int32_t)m.oneR +
-                                  (int64_t)(int32_t)partner[(r << 6) | L] * (int32_t)m.oneR;
-                acc[r] = smont_red(S, m);
-            }
-        }
-    }
-
-    if (ACCIO) {
-        uint64_t* dst = g.acc_io + ((size_t)gate * 2 + c) * g.N;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const int32_t v = (int32_t)smont_mul(acc[r], T.nR, m);
-            dst[slot_2k(L, r)] = (uint64_t)(uint32_t)(v < 0 ? v + (int32_t)m.Q : v);
-        }
-        return;
-    }
-    // extraction (binfhe-base-scheme.cpp:110-121), as k_blind_rotate_n2k
-    __syncthreads();  // the partner has read this wave's tile
-    inv_2k_s<BIN, LIM>(acc, tile, L, twAi, s_tabI, T.w1R, m.oneR, m);
-    if (c == 0) {
-        uint64_t* oa = ext_a + (size_t)gate * g.N;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const uint32_t x = ((uint32_t)r << 6) | (uint32_t)L;
-            const uint32_t v = acc[r];
-            const uint32_t o = (x == 0 || v == 0) ? v : m.Q - v;
-            oa[(g.N - x) & (g.N - 1)] = g.msb_out ? mod_switch(o, m.Q, g.qKS) : o;
-        }
-    } else if (L == 0) {
-        const uint32_t bb = add_mod(g.b_const, acc[0], m.Q);
-        ext_b[gate]       = g.msb_out ? mod_switch(bb, m.Q, g.qKS) : bb;
-    }
-}
-
-bool lmk2k_supported(const GateArgs& g, const BootTables& t, int nd) {
-    // 2 or 3 retained digits, Q < 2^29 (the forward transform reduced once at Q >= 2^27, three times at
-    // Q >= 2^28); 4 digits (STD256Q_4_LMKCDEY) at Q < 2^27.  (The 4-digit form first ran at 1.07K gates/s
-    // against 10.6K on K5, profiles/r04_ext_bench.txt: its digit array sat in scratch, the forward stage
-    // loop left rolled; the stages are now written out.)
-    const bool qok = nd == 4 ? t.Q < (1u << 27) : t.Q < (1u << 29);
-    return qok && g.N == 2048 && g.tv == nullptr && g.tv64 == nullptr && g.gbits >= 2 && nd >= 2 && nd <= 4 &&
-           (uint32_t)(nd + 1) * g.gbits <= 32;
-}
-
-hipError_t launch_blind_rotate_lmk2k(const GateArgs& g, const BootTables& t, const void* ek, const void* ak,
-                                     const uint16_t* ops, const uint32_t* nops, uint32_t maxops, const uint32_t* tvb,
-                                     uint64_t* ext_a, uint64_t* ext_b, int nd, hipStream_t s) {
-    if (g.count == 0) return hipSuccess;
-    if (!lmk2k_supported(g, t, nd)) return hipErrorInvalidValue;
-    const uint4* e = static_cast<const uint4*>(ek);
-    const uint4* a = static_cast<const uint4*>(ak);
-#define FHE_L2K(ND_, IO, QM_)                                                                                      \
-    hipLaunchKernelGGL((k_blind_rotate_lmk2k<ND_, IO, QM_>), dim3(g.count), dim3(128), l2k_lds(), s, g, t, e, a, ops,  \
-                       nops, maxops, tvb, ext_a, ext_b, t.twA_fwd, t.twA_inv)
-    const int qm = t.Q >= (1u << 28) ? 2 : t.Q >= (1u << 27) ? 1 : 0;  // the modulus class (fwd_2k_s)
-    if (nd == 2) {  // STD256Q_LMKCDEY (28-bit Q)
-        if (qm == 1) { if (g.acc_io) FHE_L2K(2, true, 1); else FHE_L2K(2, false, 1); }
-        else if (qm == 2) { if (g.acc_io) FHE_L2K(2, true, 2); else FHE_L2K(2, false, 2); }
-        else { if (g.acc_io) FHE_L2K(2, true, 0); else FHE_L2K(2, false, 0); }
-    } else if (nd == 4) {  // STD256Q_4_LMKCDEY (digitsG 5)
-        if (g.acc_io) FHE_L2K(4, true, 0); else FHE_L2K(4, false, 0);
-    } else {  // STD256Q_3_LMKCDEY (26-bit); STD256_3 / _4_LMKCDEY (29-bit)
-        if (qm == 0) { if (g.acc_io) FHE_L2K(3, true, 0); else FHE_L2K(3, false, 0); }
-        else if (qm == 1) { if (g.acc_io) FHE_L2K(3, true, 1); else FHE_L2K(3, false, 1); }
-        else { if (g.acc_io) FHE_L2K(3, true, 2); else FHE_L2K(3, false, 2); }
-    }
-#undef FHE_L2K
-    return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------
 // ExternalProduct seam (Backend::ExternalProduct[Batch], backend.h:141-146, 187-192): per-item
 // RGSW keys in the reference's raw EVAL layout [dG2 = 4][2][N] packed into the op-list kernel's
@@ -4181,35 +3265,6 @@ hipError_t launch_single_ops(uint16_t* ops, uint32_t* nops, uint32_t count, uint
     if (count == 0) return hipSuccess;
     if (count > 0x8000u) return hipErrorInvalidValue;   // op codes: key index < 0x8000
     hipLaunchKernelGGL(k_single_ops, dim3((count + 255) / 256), dim3(256), 0, s, ops, nops, count, maxops);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// ModSwitch on u64 vectors (standalone entry point)
-// ---------------------------------------------------------------------------
-// RoundqQ exactly as the reference writes it (lwe-pke.cpp:41-46): IEEE double, the product divided
-// before the add (no contraction).  Any moduli: the GPU's double divide is correctly rounded.
-FHE_DEV uint64_t round_qQ_double(uint64_t v, uint64_t to, uint64_t from) {
-#pragma clang fp contract(off)
-    const double x = (double)v * (double)to / (double)from;
-    return (uint64_t)floor(0.5 + x) % to;
-}
-
-__global__ void k_modswitch(uint64_t from, uint64_t to, uint32_t len, uint32_t count, const uint64_t* __restrict__ a,
-                            const uint64_t* __restrict__ b, uint64_t* __restrict__ ao, uint64_t* __restrict__ bo) {
-    const uint64_t total = (uint64_t)len * count;
-    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x)
-        ao[t] = round_qQ_double(a[t], to, from);
-    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < count; t += (uint64_t)gridDim.x * blockDim.x)
-        bo[t] = round_qQ_double(b[t], to, from);
-}
-
-hipError_t launch_modswitch(uint64_t q_from, uint64_t q_to, uint32_t len, uint32_t count, const uint64_t* a,
-                            const uint64_t* b, uint64_t* a_out, uint64_t* b_out, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    const uint64_t total = (uint64_t)len * count;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_modswitch, dim3(blocks), dim3(256), 0, s, q_from, q_to, len, count, a, b, a_out, b_out);
     return hipGetLastError();
 }
 

@@ -33,7 +33,7 @@ bool Engine::narrow_set(const Params& p) {
 }
 
 bool Engine::g3_set(const Params& p) {
-    // digit fields of d + C in 32 bits (bootstrap.hip decompose_n): 4 g <= 32 and C + Q < 2^32
+    // digit fields of d + C in 32 bits (boot_arith.h decompose_n): 4 g <= 32 and C + Q < 2^32
     const uint64_t g = p.gBits, h = 1ull << (g - 1);
     const uint64_t C = h * (1 + (1ull << g) + (1ull << (2 * g)) + (1ull << (3 * g)));
     return !is_large(p.paramset) && !p.timeopt && (p.method == M_GINX || p.method == M_LMKCDEY) && p.N == 1024 &&
@@ -150,7 +150,7 @@ bool Engine::ks32w_set(const Params& p) {
            keyswitch_w32_shape(p.baseKS, p.digitsKS) && p.n < 2048 && p.N <= 2048;
 }
 
-// K1w tables (bootstrap.hip k_blind_rotate_n2k): Table / TableI (2048 words each, u32 Montgomery; the
+// K1w tables (boot_n2k_ginx.hip k_blind_rotate_n2k): Table / TableI (2048 words each, u32 Montgomery; the
 // uniform stages read words 0..31 of them), the half-resolution monomial pairs psi^(2f) - 1 for
 // f in [0, 2048] at f + (f >> 5)
 void Engine::build_tables_n2k() {

@@ -195,4 +195,26 @@ hipError_t launch_switch_out(const uint64_t* a, const uint64_t* b, uint32_t stri
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// ModSwitch on u64 vectors (standalone entry point): RoundqQ exactly as the reference writes it
+// (round_qQ_ref).  Any moduli: the GPU's double divide is correctly rounded.
+// ---------------------------------------------------------------------------
+__global__ void k_modswitch(uint64_t from, uint64_t to, uint32_t len, uint32_t count, const uint64_t* __restrict__ a,
+                            const uint64_t* __restrict__ b, uint64_t* __restrict__ ao, uint64_t* __restrict__ bo) {
+    const uint64_t total = (uint64_t)len * count;
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x)
+        ao[t] = round_qQ_ref(a[t], to, from);
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < count; t += (uint64_t)gridDim.x * blockDim.x)
+        bo[t] = round_qQ_ref(b[t], to, from);
+}
+
+hipError_t launch_modswitch(uint64_t q_from, uint64_t q_to, uint32_t len, uint32_t count, const uint64_t* a,
+                            const uint64_t* b, uint64_t* a_out, uint64_t* b_out, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const uint64_t total = (uint64_t)len * count;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_modswitch, dim3(blocks), dim3(256), 0, s, q_from, q_to, len, count, a, b, a_out, b_out);
+    return hipGetLastError();
+}
+
 }  // namespace fhe_amd

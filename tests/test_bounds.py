@@ -1,4 +1,4 @@
-"""Signed 32-bit headroom of the transforms that run without reductions (fhe_amd/csrc/bootstrap.hip,
+"""Signed 32-bit headroom of the transforms that run without reductions (fhe_amd/csrc/bootstrap.hip and boot_2k.h,
 FHE_FWD_TIGHT and the QM classes of K1w), checked for the modulus of every parameter row whose kernel
 runs them.
 

@@ -39,7 +39,7 @@ def wrap32(x):
 
 
 def smont_mul(a, bR, Q):
-    """bootstrap.hip smont_mul: a (int32) * bR (< Q) * 2^-32 mod Q, in (-Q, Q)"""
+    """boot_arith.h smont_mul: a (int32) * bR (< Q) * 2^-32 mod Q, in (-Q, Q)"""
     qinvp = pow(Q, -1, 1 << 32)
     t = np.asarray(a, np.int64) * np.int64(bR)          # |a| < 2^31, bR < 2^28
     lo = (t.astype(np.uint64) & np.uint64(0xFFFFFFFF)) * np.uint64(qinvp) & np.uint64(0xFFFFFFFF)
