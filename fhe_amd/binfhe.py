@@ -154,6 +154,10 @@ def _setup(L):
     L.fhe_hip_circuit_add_input.argtypes = [vp, pu32]
     L.fhe_hip_circuit_add_not.argtypes = [vp, u32, pu32]
     L.fhe_hip_circuit_add_gate.argtypes = [vp, ctypes.c_int, u32, u32, pu32]
+    L.fhe_hip_circuit_add_gate_multi.argtypes = [vp, ctypes.c_int, vp, u32, u32, pu32]
+    L.fhe_hip_circuit_level_gate_classes.argtypes = [vp, sz, vp, vp, sz, psz]
+    L.fhe_hip_gate_window.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, u32,
+                                      *[ctypes.POINTER(ctypes.c_uint64)] * 4]
     L.fhe_hip_circuit_add_cmux.argtypes = [vp, u32, u32, u32, pu32]
     L.fhe_hip_circuit_add_bootstrap.argtypes = [vp, u32, pu32]
     L.fhe_hip_circuit_add_func.argtypes = [vp, u32, vp, sz, pu32]
@@ -420,9 +424,16 @@ def gate_fold(paramset, method, gate, ref_gate=AND):
     return q1.value, bool(dbl.value), bshift.value
 
 
+def gate_window(paramset, method, gate, p):
+    """(q1, value, b_const, bshift_to_and) of fhe_hip_gate_window: `gate`'s window at plaintext modulus p"""
+    v = [ctypes.c_uint64() for _ in range(4)]
+    check(L().fhe_hip_gate_window(paramset, method, gate, p, *(ctypes.byref(x) for x in v)))
+    return tuple(x.value for x in v)
+
+
 class Circuit:
-    """A circuit (fhe_hip_circuit): a DAG of inputs, 2-input gates, NOT, CMUX, BOOTSTRAP, FUNC (EvalFunc with a
-    LUT) and LINEAR (signed sum plus a constant) nodes built on the host, evaluated level by level on the GPU by
+    """A circuit (fhe_hip_circuit): a DAG of inputs, 2-input gates, multi-input gates, NOT, CMUX, BOOTSTRAP, FUNC
+    (EvalFunc with a LUT) and LINEAR (signed sum plus a constant) nodes built on the host, evaluated level by level on the GPU by
     GateEngine.eval_circuit.  Node ids are consecutive from 0.
 
         c = Circuit()
@@ -462,6 +473,14 @@ class Circuit:
     def gate(self, g, x, y):
         return self._add(L().fhe_hip_circuit_add_gate, g, x, y)
 
+    def gate_multi(self, g, xs, p):
+        """MAJORITY / AND3 / OR3 / AND4 / OR4 over the 2 to 4 nodes xs at plaintext modulus p
+        (GateEngine.eval_gate_multi): one bootstrap.  The caller owns the encoding of what it wires together; only
+        p = 4 nodes compose with 2-input gates and NOT."""
+        xs = [int(x) for x in xs]
+        ax = (ctypes.c_uint32 * max(len(xs), 1))(*xs)
+        return self._add(L().fhe_hip_circuit_add_gate_multi, g, ax, len(xs), p)
+
     def cmux(self, c0, c1, sel):
         """sel ? c1 : c0 (GateEngine.eval_cmux(c0, c1, sel))"""
         return self._add(L().fhe_hip_circuit_add_cmux, c0, c1, sel)
@@ -495,10 +514,19 @@ class Circuit:
         return v.value
 
     def level_classes(self, i):
-        """level i's rows in row order: (gates and BOOTSTRAP, tables at q, tables at 2q, linear)"""
+        """level i's rows in row order: (gates, BOOTSTRAP and multi-input gates at p = 4, tables at q, tables at 2q,
+        linear); level_gate_classes(i) lies between the third and the fourth"""
         w = (ctypes.c_size_t * 4)()
         check(L().fhe_hip_circuit_level_classes(self._h, i, w))
         return tuple(w)
+
+    def level_gate_classes(self, i):
+        """[(p, width)] of level i's multi-input gate classes at plaintext moduli other than 4, in row order"""
+        n = ctypes.c_size_t()
+        check(L().fhe_hip_circuit_level_gate_classes(self._h, i, None, None, 0, ctypes.byref(n)))
+        pm, w = (ctypes.c_uint32 * max(n.value, 1))(), (ctypes.c_size_t * max(n.value, 1))()
+        check(L().fhe_hip_circuit_level_gate_classes(self._h, i, pm, w, n.value, None))
+        return [(int(pm[j]), int(w[j])) for j in range(n.value)]
 
     def tables(self, paramset, method, cls):
         """the distinct scaled test-vector tables of launch class cls (1: at q, 2: at 2q) as [n_tables][ctmod]"""

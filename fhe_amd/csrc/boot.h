@@ -113,8 +113,9 @@ hipError_t launch_prep_ginx(const GateArgs& g, const GateInputs& in, uint16_t* i
 // One launch class of a circuit level (circuit.h) as prep input: B instances of `nodes` slots, operands read by
 // row from the ciphertext pool pool_a [rows][n] / pool_b [rows] (u64, mod q; a class-2 first stage's row mod 2q).
 // Slot s of the class is node s / B, instance s % B, its operands the rows src B + instance of desc[node];
-// a launch covers slots [first, first + g.count).  Class 0 (gates of any 2-input types and BOOTSTRAP nodes): the
-// launch's GateArgs are AND's, every node's window is moved onto it by its bshift.  Classes 1 and 2 (FUNC
+// a launch covers slots [first, first + g.count).  Class 0 (gates of any 2-input types, BOOTSTRAP nodes, multi-input
+// gates at plaintext modulus 4) and the gate classes of the other plaintext moduli: the launch's GateArgs are AND's
+// window with the modulus's Q/(2p) + 1, every node's window is moved onto it by its bshift.  Classes 1 and 2 (FUNC
 // nodes): GateArgs with the class's tables in tv / tv64 and its ctmod; the prep writes each slot's table index
 // into the high half of tvb (DESIGN.md §4 "Circuits").
 struct CircuitLevel {

@@ -602,24 +602,43 @@ struct PoolFetch {
     const uint64_t* pb;       // [rows]
     const CircuitSlot* desc;  // the level's nodes
     uint32_t B, first;
-    FHE_DEV uint32_t sum(const CircuitSlot& d, uint32_t x0, uint32_t x1, uint32_t boff, uint32_t qm) const {
-        uint32_t s = boff + ((d.flags & CircuitSlot::kNeg0) ? 0u - x0 : x0);
-        if (!(d.flags & CircuitSlot::kOne)) s += (d.flags & CircuitSlot::kNeg1) ? 0u - x1 : x1;
+    // the node's descriptor as two 16-byte loads, whole before any operand is fetched: left to itself the compiler
+    // narrows them to the fields and defers src[1..3] to where they are used, one more dependent round trip each
+    FHE_DEV CircuitSlot slot(uint32_t node) const {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4* p = reinterpret_cast<const u32x4*>(desc + node);
+        u32x4 lo = p[0], hi = p[1];
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        return CircuitSlot{{lo.x, lo.y, lo.z, lo.w}, hi.x, hi.y, hi.z, hi.w};
+    }
+    // word `at` (+ stride per row) of the node's d.k operand rows, summed with their signs.  Rows 0 and 1 are
+    // fetched together and unconditionally, as before the multi-input gates (a one-operand slot names its row
+    // twice); rows 2 and 3 together under a branch on d.k > 2, which is the same in every lane that works on one
+    // node (a wave of k_prep_ginx that straddles two nodes takes both sides once), a three-operand slot naming
+    // its last row twice.  A slot with one or two operands issues the loads it always did.
+    FHE_DEV uint32_t sum(const CircuitSlot& d, const uint64_t* p, size_t stride, size_t at, uint32_t boff, uint32_t qm) const {
+        const uint32_t f = d.flags / CircuitSlot::kNeg;
+        const uint32_t x0 = (uint32_t)p[d.src[0] * stride + at], x1 = (uint32_t)p[d.src[1] * stride + at];
+        uint32_t s = boff + ((f & 1) ? 0u - x0 : x0);
+        s += ((f & 2) ? 0u - x1 : x1) & (d.k > 1 ? ~0u : 0u);  // masked, not branched over: both loads stay in flight
+        if (d.k > 2) {
+            const uint32_t x2 = (uint32_t)p[d.src[2] * stride + at], x3 = (uint32_t)p[d.src[3] * stride + at];
+            s += (f & 4) ? 0u - x2 : x2;
+            s += ((f & 8) ? 0u - x3 : x3) & (d.k > 3 ? ~0u : 0u);
+        }
         s &= qm;
         return (d.flags & CircuitSlot::kDbl) ? (2 * s) & qm : s;
     }
     FHE_DEV uint32_t a(size_t t, uint32_t n, uint32_t qm) const {
         const uint32_t gate = (uint32_t)(t / n), i = (uint32_t)(t - (size_t)gate * n);
         const uint32_t s = first + gate, node = s / B, inst = s - node * B;
-        const CircuitSlot d = desc[node];
-        return sum(d, (uint32_t)pa[((size_t)d.src0 * B + inst) * n + i], (uint32_t)pa[((size_t)d.src1 * B + inst) * n + i],
-                   0, qm);
+        const CircuitSlot d = slot(node);
+        return sum(d, pa, (size_t)B * n, (size_t)inst * n + i, 0, qm);
     }
     FHE_DEV uint32_t b(uint32_t gate, uint32_t qm) const {
         const uint32_t s = first + gate, node = s / B, inst = s - node * B;
-        const CircuitSlot d = desc[node];
-        const uint32_t v = sum(d, (uint32_t)pb[(size_t)d.src0 * B + inst], (uint32_t)pb[(size_t)d.src1 * B + inst],
-                               d.boff_pre, qm);
+        const CircuitSlot d = slot(node);
+        const uint32_t v = sum(d, pb, B, inst, d.boff_pre, qm);
         // table slots (FUNC nodes): the slot's table index travels in the high half of tvb (0 for gates)
         return ((v + d.bshift) & qm) | (d.flags & CircuitSlot::kTableMask);
     }

@@ -1142,6 +1142,15 @@ int fhe_hip_circuit_add_gate(fhe_hip_circuit* c, int gate, uint32_t x, uint32_t 
     });
 }
 
+int fhe_hip_circuit_add_gate_multi(fhe_hip_circuit* c, int gate, const uint32_t* xs, uint32_t k, uint32_t ptmod,
+                                   uint32_t* id) {
+    if (!c || !id || (k && !xs)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        *id = c->c.add_gate_multi(gate, xs, k, ptmod);
+        return FHE_HIP_OK;
+    });
+}
+
 int fhe_hip_circuit_add_cmux(fhe_hip_circuit* c, uint32_t c0, uint32_t c1, uint32_t sel, uint32_t* id) {
     if (!c || !id) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
     return guarded([&]() -> int {
@@ -1180,6 +1189,24 @@ int fhe_hip_circuit_level_classes(const fhe_hip_circuit* c, size_t level, size_t
     if (!c->c.finalized()) return fail(FHE_HIP_ERR_NOT_INIT, "circuit is not finalized");
     return guarded([&]() -> int {
         c->c.level_classes(level, widths);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_circuit_level_gate_classes(const fhe_hip_circuit* c, size_t level, uint32_t* ptmods, size_t* widths, size_t cap,
+                                       size_t* n_classes) {
+    if (!c) return fail(FHE_HIP_ERR_NULL_PTR, "circuit is null");
+    if (!c->c.finalized()) return fail(FHE_HIP_ERR_NOT_INIT, "circuit is not finalized");
+    return guarded([&]() -> int {
+        const auto& gcs = c->c.level_gate_classes(level);
+        if (n_classes) *n_classes = gcs.size();
+        if (ptmods || widths) {
+            if (cap < gcs.size()) throw std::invalid_argument("circuit gate classes: the buffer is too small");
+            for (size_t i = 0; i < gcs.size(); ++i) {
+                if (ptmods) ptmods[i] = gcs[i].first;
+                if (widths) widths[i] = gcs[i].second;
+            }
+        }
         return FHE_HIP_OK;
     });
 }
@@ -1266,6 +1293,19 @@ int fhe_hip_gate_fold(int paramset, int method, int gate, int ref_gate, uint32_t
         *dbl = f.dbl;
         *bshift = f.bshift;
         *q1 = f.q1;
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_gate_window(int paramset, int method, int gate, uint32_t ptmod, uint64_t* q1, uint64_t* value,
+                        uint64_t* b_const, uint64_t* bshift_to_and) {
+    if (!q1 || !value || !b_const || !bshift_to_and) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        const GateWindow w = gate_window(make_params(paramset, method), gate, ptmod);
+        *q1 = w.q1;
+        *value = w.value;
+        *b_const = w.b_const;
+        *bshift_to_and = w.bshift_to_and;
         return FHE_HIP_OK;
     });
 }

@@ -18,6 +18,10 @@ bool two_input(int gate) {
             return false;
     }
 }
+
+bool multi_input(int gate) {
+    return gate == G_MAJORITY || gate == G_AND3 || gate == G_OR3 || gate == G_AND4 || gate == G_OR4;
+}
 }  // namespace
 
 // checkInputFunction (binfhe-base-scheme.h:245-260): 0 negacyclic, 1 periodic, 2 arbitrary
@@ -66,6 +70,13 @@ GateFold gate_fold(const Params& p, int gate, int ref_gate) {
     return f;
 }
 
+GateWindow gate_window(const Params& p, int gate, uint32_t ptmod) {
+    if (!two_input(gate) && !multi_input(gate)) throw std::invalid_argument("gate window: unsupported gate");
+    if (ptmod < 2 || 2ull * ptmod > p.q) throw std::invalid_argument("plaintext modulus out of range");
+    const uint64_t q = p.q, q1 = p.gate_const(gate), value = p.Q / (2ull * ptmod) + 1;
+    return GateWindow{q1, value, multi_input(gate) ? value : (p.Q >> 3) + 1, (p.gate_const(G_AND) + q - q1) % q};
+}
+
 void Circuit::check_open() const {
     if (finalized_) throw std::invalid_argument("circuit is finalized: no node or output can be added");
 }
@@ -85,7 +96,7 @@ uint32_t Circuit::push(Kind k, int gate, uint32_t a, uint32_t b, uint32_t c, Ref
 Circuit::Ref Circuit::new_phys(int gate, Ref x, Ref y) {
     if (two_input(gate) && x.phys == y.phys && x.neg == y.neg)
         throw std::invalid_argument("circuit: a gate's input ciphertexts must be independent");
-    phys_.push_back(Phys{gate, x, y, 0, 0, 0, 0, 0});
+    phys_.push_back(Phys{gate, x, y, 0, 0, 0, 0, 0, {Ref{0, 0}, Ref{0, 0}}, 0, 0});
     return Ref{(uint32_t)(phys_.size() - 1), 0};
 }
 
@@ -109,6 +120,33 @@ uint32_t Circuit::add_gate(int gate, uint32_t x, uint32_t y) {
     check_id(x);
     check_id(y);
     return push(K_GATE, gate, x, y, 0, new_phys(gate, ref_[x], ref_[y]));
+}
+
+uint32_t Circuit::add_gate_multi(int gate, const uint32_t* xs, size_t k, uint32_t ptmod) {
+    check_open();
+    if (!multi_input(gate))
+        throw std::invalid_argument("circuit: a multi-input node is AND3, OR3, AND4, OR4 or MAJORITY");
+    if (k < 2 || k > 4) throw std::invalid_argument("EvalBinGate(ctvector): 2 to 4 ciphertexts");
+    if (!xs) throw std::invalid_argument("circuit: a multi-input node needs operands");
+    if (ptmod < 2) throw std::invalid_argument("plaintext modulus out of range");
+    Ref r[4] = {};
+    for (size_t j = 0; j < k; ++j) {
+        check_id(xs[j]);
+        r[j] = ref_[xs[j]];
+        for (size_t i = 0; i < j; ++i)  // the reference's pairwise check (binfhe-base-scheme.cpp:136-143)
+            if (r[i].phys == r[j].phys && r[i].neg == r[j].neg)
+                throw std::invalid_argument("circuit: a gate's input ciphertexts must be independent");
+    }
+    if (nodes_.size() >= 0x7fffffffu) throw std::invalid_argument("circuit too large");
+    // every refusal is above: from here on the node is added
+    const Ref out = new_phys(gate, r[0], r[1]);
+    Phys& p = phys_[out.phys];
+    p.z[0] = r[2];
+    p.z[1] = r[3];
+    p.k = (uint32_t)k;
+    p.ptmod = ptmod;
+    max_ptmod_ = std::max(max_ptmod_, ptmod);
+    return push(K_MULTI, gate, xs[0], xs[1], k > 2 ? xs[2] : 0, out);
 }
 
 uint32_t Circuit::add_cmux(uint32_t c0, uint32_t c1, uint32_t sel) {
@@ -247,50 +285,72 @@ void Circuit::finalize() {
             p.level = 0;
             for (uint32_t j = 0; j < ln.k; ++j) p.level = std::max(p.level, phys_[ln.x[j].phys].level);
         } else {
-            p.level = 1 + (p.gate == kBoot ? phys_[p.x.phys].level : std::max(phys_[p.x.phys].level, phys_[p.y.phys].level));
+            p.level = p.gate == kBoot ? phys_[p.x.phys].level : std::max(phys_[p.x.phys].level, phys_[p.y.phys].level);
+            for (uint32_t j = 2; j < p.k; ++j) p.level = std::max(p.level, phys_[p.z[j - 2].phys].level);
+            ++p.level;
         }
         top = std::max(top, p.level);
     }
-    // a level's rows: class 0, class 1, class 2 (first stages, then second stages), LINEAR; level 0: the inputs first
+    // a level's rows: class 0 (with the multi-input gates at plaintext modulus 4), class 1, class 2 (first stages,
+    // then second stages), the gate classes of the other plaintext moduli in ascending order, LINEAR; level 0: the
+    // inputs first.  Groups 0..3 and 5 are fixed; group 4 is split by modulus.
     auto order = [](const Phys& p) -> int {
-        if (p.gate == kLinear) return 4;
+        if (p.gate == kLinear) return 5;
+        if (p.ptmod && p.ptmod != 4) return 4;
         if (p.gate == kInput || p.cls == 0) return 0;
         return p.cls == 1 ? 1 : 1 + p.stage;
     };
-    std::vector<size_t> cnt((size_t)(top + 1) * 5, 0);
-    for (const Phys& p : phys_) ++cnt[(size_t)p.level * 5 + order(p)];
+    std::vector<size_t> cnt((size_t)(top + 1) * 6, 0);
+    std::vector<std::map<uint32_t, size_t>> extra(top + 1);  // per level: ptmod -> width, then -> next row
+    for (const Phys& p : phys_) {
+        const int o = order(p);
+        ++cnt[(size_t)p.level * 6 + o];
+        if (o == 4) ++extra[p.level][p.ptmod];
+    }
     level_row_.assign(top + 2, 0);
     plan_.assign(top + 1, LevelPlan{});
-    std::vector<size_t> next((size_t)(top + 1) * 5, 0);
+    std::vector<size_t> next((size_t)(top + 1) * 6, 0);
     size_t n_slots = 0, n_lins = 0;
     for (uint32_t l = 0; l <= top; ++l) {
-        const size_t* c = &cnt[(size_t)l * 5];
+        const size_t* c = &cnt[(size_t)l * 6];
+        LevelPlan& lp = plan_[l];
         size_t row = level_row_[l];
-        for (int o = 0; o < 5; ++o) {
-            next[(size_t)l * 5 + o] = row;
-            row += c[o];
+        for (int o = 0; o < 6; ++o) {
+            next[(size_t)l * 6 + o] = row;
+            if (o == 4) {
+                for (auto& e : extra[l]) {
+                    lp.extra.emplace_back(e.first, e.second);
+                    const size_t width = e.second;
+                    e.second = row;
+                    row += width;
+                }
+            } else {
+                row += c[o];
+            }
         }
         level_row_[l + 1] = row;
-        LevelPlan& lp = plan_[l];
         lp.w[0] = l ? c[0] : 0;
         lp.w[1] = c[1];
         lp.w[2] = c[2] + c[3];
-        lp.w[3] = c[4];
+        lp.w[3] = c[5];
         lp.arb1 = c[2];
         lp.slot = n_slots;
         lp.lin = n_lins;
-        n_slots += lp.w[0] + lp.w[1] + lp.w[2];
+        lp.xw = c[4];
+        n_slots += lp.w[0] + lp.w[1] + lp.w[2] + lp.xw;
         n_lins += lp.w[3];
     }
     slots_.assign(n_slots, 0);
     lins_.assign(n_lins, 0);
     for (uint32_t i = 0; i < phys_.size(); ++i) {
         Phys& p = phys_[i];
-        p.row = (uint32_t)next[(size_t)p.level * 5 + order(p)]++;
+        const int o = order(p);
+        p.row = (uint32_t)(o == 4 ? extra[p.level][p.ptmod]++ : next[(size_t)p.level * 6 + o]++);
         if (p.gate == kInput) continue;
+        // bootstrapped rows come first in a level (after the inputs in level 0), LINEAR rows last
         const LevelPlan& lp = plan_[p.level];
         const size_t in_level = p.row - level_row_[p.level] - (p.level ? 0 : n_in_);
-        if (p.gate == kLinear) lins_[lp.lin + in_level - (lp.w[0] + lp.w[1] + lp.w[2])] = i;
+        if (p.gate == kLinear) lins_[lp.lin + in_level - (lp.w[0] + lp.w[1] + lp.w[2] + lp.xw)] = i;
         else slots_[lp.slot + in_level] = i;
     }
     static std::atomic<uint64_t> counter{0};
@@ -314,6 +374,12 @@ void Circuit::level_classes(size_t level, size_t w[4]) const {
     if (!finalized_) throw std::logic_error("circuit is not finalized");
     if (level >= plan_.size()) throw std::invalid_argument("circuit: no such level");
     for (int j = 0; j < 4; ++j) w[j] = plan_[level].w[j];
+}
+
+const std::vector<std::pair<uint32_t, size_t>>& Circuit::level_gate_classes(size_t level) const {
+    if (!finalized_) throw std::logic_error("circuit is not finalized");
+    if (level >= plan_.size()) throw std::invalid_argument("circuit: no such level");
+    return plan_[level].extra;
 }
 
 size_t Circuit::level_arb_stage1(size_t level) const {
@@ -353,39 +419,48 @@ std::vector<CircuitSlot> Circuit::slots(const Params& p) const {
     for (size_t i = 0; i < slots_.size(); ++i) {
         const Phys& ph = phys_[slots_[i]];
         CircuitSlot& d = out[i];
-        d.src0 = phys_[ph.x.phys].row;
+        d = CircuitSlot{};
+        d.src[0] = phys_[ph.x.phys].row;
+        d.k = 1;
         if (ph.gate == kTable) {  // EvalFunc's stages (fb.cpp eval_func_device), at the class's modulus
             const uint32_t cm = table_ctmod(p, ph.cls), beta = (uint32_t)(kBeta % cm);
             d.flags = ph.aux << CircuitSlot::kTableShift;
-            d.bshift = 0;
             if (ph.y.phys == ph.x.phys) {  // x + beta: negacyclic, or a first stage
-                d.src1 = d.src0;
-                d.flags |= CircuitSlot::kOne;
                 d.boff_pre = beta;
             } else {  // x - first stage + beta - q/4 (periodic) or - q/2 (arbitrary, mod 2q)
-                d.src1 = phys_[ph.y.phys].row;
-                d.flags |= CircuitSlot::kNeg1;
+                d.src[1] = phys_[ph.y.phys].row;
+                d.k = 2;
+                d.flags |= CircuitSlot::kNeg << 1;
                 d.boff_pre = (beta + cm - (ph.cls == 2 ? q >> 1 : q4)) % cm;
             }
             continue;
         }
-        d.flags = ph.x.neg ? CircuitSlot::kNeg0 : 0u;
-        d.boff_pre = ph.x.neg ? q4 : 0u;
         if (ph.gate == kBoot) {  // Bootstrap: ct + q/4 in the AND window (binfhe-base-scheme.cpp:190-205)
-            d.src1 = d.src0;
-            d.flags |= CircuitSlot::kOne;
-            d.boff_pre = (d.boff_pre + q4) % q;
-            d.bshift = 0;
+            d.flags = ph.x.neg ? CircuitSlot::kNeg : 0u;
+            d.boff_pre = ((ph.x.neg ? q4 : 0u) + q4) % q;
             continue;
         }
-        d.src1 = phys_[ph.y.phys].row;
-        if (ph.y.neg) {
-            d.flags |= CircuitSlot::kNeg1;
-            d.boff_pre = (d.boff_pre + q4) % q;
+        // a gate over k operands: EvalNOT of an operand is a sign flip and q/4 (:223-236)
+        const Ref ops[4] = {ph.x, ph.y, ph.z[0], ph.z[1]};
+        d.k = ph.ptmod ? ph.k : 2;
+        for (uint32_t j = 0; j < d.k; ++j) {
+            d.src[j] = phys_[ops[j].phys].row;
+            if (ops[j].neg) {
+                d.flags |= CircuitSlot::kNeg << j;
+                d.boff_pre = (d.boff_pre + q4) % q;
+            }
+        }
+        if (ph.ptmod) {  // multi-input: the sum as it is, its window moved onto AND's
+            d.bshift = (uint32_t)((p.gate_const(G_AND) + q - p.gate_const(ph.gate)) % q);
+            continue;
         }
         const GateFold f = gate_fold(p, ph.gate, G_AND);
         if (f.dbl) d.flags |= CircuitSlot::kDbl;
         d.bshift = f.bshift;
+    }
+    for (CircuitSlot& d : out) {  // the rows PoolFetch fetches in pairs
+        if (d.k == 1) d.src[1] = d.src[0];
+        if (d.k == 3) d.src[3] = d.src[2];
     }
     return out;
 }
@@ -425,6 +500,8 @@ size_t Circuit::num_tables(int cls) const {
 }
 
 void Circuit::check_params(const Params& p) const {
+    if (2ull * max_ptmod_ > p.q)  // Engine::gate_args' rule for the per-gate path
+        throw std::invalid_argument("plaintext modulus out of range");
     for (const auto& l : luts_)
         if (l.size() != p.q) throw std::invalid_argument("circuit: a FUNC node's LUT length must equal the ciphertext modulus q");
     if (!tabs_[2].empty()) {

@@ -3,12 +3,26 @@
 //
 // The counterpart of the reference's BatchDAG (src/binfhe/include/batch/binfhe-batch.h:229-279), whose
 // Execute runs one gate at a time (src/binfhe/lib/batch/batch.cpp:429-482).  Here every level of the DAG
-// is up to three launch classes, each one prep + blind rotation + key switch over all of its slots
+// is a few launch classes, each one prep + blind rotation + key switch over all of its slots
 // (DESIGN.md §4 "Circuits"):
-//   class 0  gates of any 2-input types and BOOTSTRAP nodes, in AND's window,
+//   class 0  gates of any 2-input types, BOOTSTRAP nodes and the multi-input gates at plaintext modulus 4, in
+//            AND's window,
 //   class 1  test-vector tables at ciphertext modulus q (FUNC nodes with negacyclic and periodic LUTs),
 //   class 2  tables at 2q (FUNC nodes with arbitrary LUTs),
+//   one more gate class per plaintext modulus other than 4 that the level's multi-input gates use, in ascending
+//   order of the modulus: AND's window again, with the values Q/(2p) + 1 of that modulus,
 // followed by one element-wise launch for the level's LINEAR nodes (no bootstrap).
+//
+// MULTI(gate, xs[k], p), gate one of MAJORITY / AND3 / OR3 / AND4 / OR4 and 2 <= k <= 4, is EvalBinGate(gate,
+// ctvector) (binfhe-base-scheme.cpp:127-170) at plaintext modulus p: one bootstrap of the sum of its operands.
+// BootstrapGateCore gives every gate the half-circle window [q1, q1 + q/2) (:535-553), so bshift = q1(AND) - q1(gate)
+// folds it onto AND's window as it does for the 2-input gates; what differs between plaintext moduli is the value
+// Q/(2p) + 1 the accumulator kernels take per launch, hence the class per modulus.  At p = 4 that value is AND's,
+// and MAJORITY's window is AND's: a MAJORITY node is a class-0 slot with three operands and bshift = 0.  An
+// operand may be any node; a NOT alias folds in as a sign flip and q/4, as for 2-input gates.  The circuit does
+// not type-check encodings (the reference takes p from ctvector[0]): the caller owns the plaintext modulus of what
+// it wires together, and only p = 4 nodes compose with 2-input gates and NOT.  The number of distinct moduli in
+// a circuit or a level is not capped.
 //
 // FUNC(x, lut) is EvalFunc (binfhe-base-scheme.cpp:241-337), expanded by the plan into the one or two
 // bootstraps Engine::eval_func_device sequences; its class (checkInputFunction) is fixed when the node is added.
@@ -22,7 +36,6 @@
 // alias operand folds in as a sign flip and +-q/4; a LINEAR operand is refused (the caller flattens it).
 //
 // Not supported, refused when the node is added (std::invalid_argument, FHE_HIP_ERR_INVALID_PARAM):
-//   - the multi-input gates AND3 / OR3 / AND4 / OR4 / MAJORITY (their own lv / uv / b_const: no shared launch),
 //   - inputs mod Q (every input is a ciphertext mod q of dimension n),
 //   - more than 65535 tables in one class (the table index is 16 bits of the prep's output word).
 #pragma once
@@ -38,7 +51,7 @@
 namespace fhe_amd {
 
 // The ciphertext one slot of a level launch bootstraps (bootstrap.hip PoolFetch):
-//   ct = sum_j (-1)^{neg_j} pool[src_j B + inst] + (0, boff_pre) mod ctmod, doubled when dbl, then b += bshift.
+//   ct = sum_{j < k} (-1)^{neg_j} pool[src_j B + inst] + (0, boff_pre) mod ctmod, doubled when dbl, then b += bshift.
 // ctmod is the launch's: q for gates and class-1 tables, 2q for class-2 tables (operands mod q are lifted
 // with their values unchanged, binfhe-base-scheme.cpp:278-281).
 // boff_pre: q/4 per negated operand (EvalNOT, binfhe-base-scheme.cpp:223-236) plus q/4 for BOOTSTRAP (:201);
@@ -47,11 +60,14 @@ namespace fhe_amd {
 // Table slots carry their table's index within the class in the high half of flags; the prep hands it to the
 // accumulator kernels in the high half of its b word (tvb).
 struct CircuitSlot {
-    uint32_t src0, src1;  // pool rows of the operands (src1 unused when kOne)
-    uint32_t flags;
+    uint32_t src[4];  // pool rows of the operands; k = 1: src[1] = src[0], k = 3: src[3] = src[2] (fetched, not
+                      // used: PoolFetch reads rows in pairs), src[2..3] = 0 for k <= 2 (not fetched)
+    uint32_t k;       // 1 (BOOTSTRAP, x + beta of a FUNC) .. 4; 2-input gates and FUNC second stages: 2
+    uint32_t flags;   // kNeg << j: operand j is subtracted
     uint32_t boff_pre, bshift;
-    static constexpr uint32_t kNeg0 = 1, kNeg1 = 2, kDbl = 4, kOne = 8, kTableMask = 0xffff0000u, kTableShift = 16;
+    static constexpr uint32_t kDbl = 4, kNeg = 0x100, kTableMask = 0xffff0000u, kTableShift = 16;
 };
+static_assert(sizeof(CircuitSlot) == 32, "CircuitSlot is read as two 16-byte words");
 
 // A LINEAR row (circuit_gather.hip k_circuit_linear): sum_{j < k} (-1)^{neg_mask bit j} pool[src_j B + inst] + (0, c) mod q
 struct CircuitLinear {
@@ -77,6 +93,15 @@ struct GateFold {
 };
 GateFold gate_fold(const Params& p, int gate, int ref_gate);
 
+// BootstrapGateCore's window of any gate but CMUX at plaintext modulus ptmod (binfhe-base-scheme.cpp:535-556): its
+// start q1, the value Q/(2 ptmod) + 1 the test vector holds (+-), the b the extraction adds (Q/(2 ptmod) + 1 for
+// the multi-input gates, :162; (Q >> 3) + 1 for the 2-input ones whatever ptmod, :118) and q1(AND) - q1 mod q.
+// std::invalid_argument for CMUX or an unknown code, ptmod < 2 or 2 ptmod > q.
+struct GateWindow {
+    uint64_t q1, value, b_const, bshift_to_and;
+};
+GateWindow gate_window(const Params& p, int gate, uint32_t ptmod);
+
 class Circuit {
 public:
     // Nodes get consecutive ids from 0 in the order they are added; operands must be existing ids, so the
@@ -88,6 +113,11 @@ public:
     uint32_t add_input();
     uint32_t add_not(uint32_t x);                                // no bootstrap: an alias (node, negated)
     uint32_t add_gate(int gate, uint32_t x, uint32_t y);
+    // EvalBinGate(gate, ctvector) for MAJORITY / AND3 / OR3 / AND4 / OR4 over 2 <= k <= 4 operands (the rule of
+    // Engine::eval_gate_multi_device) at plaintext modulus ptmod >= 2.  Refused: any other gate code, k out of
+    // range, two operands on one (node, negation) pair (the reference's pairwise check, :136-143;
+    // MAJORITY(x, NOT x, y) is three different ciphertexts).  2 ptmod > q is refused by check_params.
+    uint32_t add_gate_multi(int gate, const uint32_t* xs, size_t k, uint32_t ptmod);
     uint32_t add_cmux(uint32_t c0, uint32_t c1, uint32_t sel);   // sel ? c1 : c0, as Engine::cmux_levels folds it
     uint32_t add_bootstrap(uint32_t x);                          // BinFHEScheme::Bootstrap
     // EvalFunc(x, lut): len a power of two >= 4, every value < len; x not a NOT alias (header comment)
@@ -122,7 +152,11 @@ public:
     int func_class(uint32_t id) const;
     // A level's rows, in row order: w[0..2] the bootstraps of launch classes 0..2 (each one contiguous block;
     // within class 2 the first stages come first), w[3] its LINEAR rows.  Level 0: inputs are not counted.
+    // w[0] includes the multi-input gates at plaintext modulus 4.  The gate classes of the other plaintext moduli
+    // lie between class 2 and the LINEAR rows and are not in w: level_gate_classes.
     void level_classes(size_t level, size_t w[4]) const;
+    // the level's (plaintext modulus, width) pairs of those extra gate classes, in row order (ascending modulus)
+    const std::vector<std::pair<uint32_t, size_t>>& level_gate_classes(size_t level) const;
     size_t level_arb_stage1(size_t level) const;  // first-stage slots at the head of the level's class 2
     size_t level_slot(size_t level) const;        // index in slots() of the level's first bootstrap
     size_t level_linear(size_t level) const;      // index in linears() of the level's first LINEAR row
@@ -138,10 +172,11 @@ public:
     size_t num_tables(int cls) const;
     static uint32_t table_ctmod(const Params& p, int cls) { return cls == 2 ? 2 * p.q : p.q; }
     std::vector<uint64_t> tables(const Params& p, int cls) const;
-    void check_params(const Params& p) const;  // the refusals of tables(), for both classes
+    // the refusals of tables(), for both classes, and a multi-input gate's plaintext modulus with 2 ptmod > q
+    void check_params(const Params& p) const;
 
 private:
-    enum Kind : uint8_t { K_INPUT, K_NOT, K_GATE, K_CMUX, K_BOOTSTRAP, K_FUNC, K_LINEAR };
+    enum Kind : uint8_t { K_INPUT, K_NOT, K_GATE, K_CMUX, K_BOOTSTRAP, K_FUNC, K_LINEAR, K_MULTI };
     struct Node {
         Kind kind;
         int gate;
@@ -150,15 +185,18 @@ private:
     struct Ref {  // a bootstrapped node or input, possibly negated
         uint32_t phys, neg;
     };
-    // an input (gate = kInput), one bootstrap: a 2-input gate, BOOTSTRAP (gate = kBoot) or a table slot (gate =
+    // an input (gate = kInput), one bootstrap: a 2-input gate, BOOTSTRAP (gate = kBoot), a table slot (gate =
     // kTable: launch class cls, stage 1 or 2 of EvalFunc, aux = its table in the class; y = the first stage's
-    // row in stage 2 of a two-stage class), or a LINEAR row (gate = kLinear, aux = index in lin_)
+    // row in stage 2 of a two-stage class) or a multi-input gate (k operands x, y, z[0], z[1]; ptmod), or a
+    // LINEAR row (gate = kLinear, aux = index in lin_)
     struct Phys {
         int gate;
         Ref x, y;
         uint32_t level, row;
         uint8_t cls, stage;
         uint32_t aux;
+        Ref z[2];
+        uint32_t k, ptmod;  // ptmod: 0 for everything but a multi-input gate
     };
     struct Lin {
         Ref x[4];
@@ -189,12 +227,14 @@ private:
     std::map<std::pair<int, uint32_t>, uint32_t> tab_ids_[3];       // (kind, lut) -> index in tabs_[cls]
     std::map<std::pair<uint32_t, int>, uint32_t> stage1_;           // (operand phys, class) -> shared first stage
     size_t n_in_ = 0, max_slots_ = 0;
+    uint32_t max_ptmod_ = 0;  // the largest plaintext modulus of a multi-input gate
     bool finalized_ = false;
     uint64_t serial_ = 0;
     // after finalize(): phys indices of the bootstrapped rows and of the LINEAR rows in pool-row order, first row
     // per level (+ end), and per level: class widths, first-stage count of class 2, first slot, first LINEAR
     struct LevelPlan {
-        size_t w[4], arb1, slot, lin;
+        size_t w[4], arb1, slot, lin, xw;
+        std::vector<std::pair<uint32_t, size_t>> extra;  // (ptmod, width) of the gate classes after class 2; xw their sum
     };
     std::vector<uint32_t> slots_, lins_;
     std::vector<size_t> level_row_;

@@ -1,5 +1,6 @@
 // circuit_engine.cpp -- Engine::eval_circuit_device: a finalized Circuit (circuit.h) evaluated level by level
-// on the device.  Per level and launch class (gates in AND's window, tables at q, tables at 2q): indexed prep
+// on the device.  Per level and launch class (gates in AND's window, tables at q, tables at 2q, multi-input gates
+// per plaintext modulus other than 4): indexed prep
 // over the class's slots (bootstrap.hip PoolFetch), the unchanged blind rotation (rotate_device picks the kernel
 // by the launch's slot count), the unchanged key switch straight into the class's block of pool rows; then the
 // level's LINEAR rows in one element-wise launch.  DESIGN.md §4 "Circuits".
@@ -47,6 +48,7 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         size_t w[4];
         c.level_classes(l, w);
         widest = std::max(widest, std::max(w[0], std::max(w[1], w[2])) * B);
+        for (const auto& gc : c.level_gate_classes(l)) widest = std::max(widest, gc.second * B);
     }
     // the pool: every node's B ciphertexts, no row reuse; refused when it would not fit
     const size_t pool_bytes = rows * B * (n + 1) * 8;
@@ -101,9 +103,12 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
     const CircuitOut* d_outs = reinterpret_cast<const CircuitOut*>(dbase + desc_bytes);
     const CircuitLinear* d_lins = reinterpret_cast<const CircuitLinear*>(dbase + lin_off);
 
-    // the launch's arguments per class: AND's window, or the class's tables as bootstrap_func_tables builds them
-    auto class_args = [&](int cls, size_t cnt) {
+    // the launch's arguments per class: AND's window, the class's tables as bootstrap_func_tables builds them, or
+    // (cls 3) AND's window with lv / uv / b_const from Q/(2 ptmod) + 1 -- which is what gate_args builds for
+    // MAJORITY at that modulus, q1(MAJORITY) being q1(AND)
+    auto class_args = [&](int cls, size_t cnt, uint32_t ptmod) {
         if (cls == 0) return gate_args(G_AND, cnt);
+        if (cls == 3) return gate_args(G_MAJORITY, cnt, ptmod, true);
         GateArgs g{};
         g.count = (uint32_t)cnt;
         g.n = p_.n;
@@ -139,13 +144,16 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         size_t w[4];
         c.level_classes(l, w);
         size_t row0 = c.level_row(l), slot0 = c.level_slot(l);
-        for (int cls = 0; cls < 3; ++cls) {
-            const size_t width = w[cls], total = width * B;
+        const auto& gcs = c.level_gate_classes(l);
+        for (size_t ci = 0; ci < 3 + gcs.size(); ++ci) {  // the level's classes in row order
+            const int cls = ci < 3 ? (int)ci : 3;
+            const uint32_t ptmod = ci < 3 ? 0 : gcs[ci - 3].first;
+            const size_t width = ci < 3 ? w[ci] : gcs[ci - 3].second, total = width * B;
             if (!width) continue;
             const uint64_t fmod = cls == 2 ? cm2 : p_.q;  // every stage's output modulus is its ciphertext modulus
             for (size_t first = 0; first < total; first += chunk) {
                 const size_t cnt = std::min(chunk, total - first);
-                const GateArgs g = class_args(cls, cnt);
+                const GateArgs g = class_args(cls, cnt, ptmod);
                 const CircuitLevel lv{pool_a, pool_b, d_slots + slot0, (uint32_t)width, (uint32_t)B, (uint32_t)first};
                 prep_level_device(g, lv, s);
                 rotate_device(g, s);

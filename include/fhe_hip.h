@@ -338,6 +338,8 @@ int fhe_hip_unpack_keys(int paramset, int method, const uint8_t* bsk_packed, siz
  *   input      a circuit input (a ciphertext mod q, dimension n)
  *   not        EvalNOT (binfhe-base-scheme.cpp:223-236): costs no bootstrap, folded into its users
  *   gate       OR, AND, NOR, NAND, XOR, XNOR, XOR_FAST, XNOR_FAST on two nodes
+ *   gate_multi MAJORITY, AND3, OR3, AND4, OR4 on 2 to 4 nodes at a plaintext modulus p (EvalBinGate(gate, ctvector),
+ *              :127-170): one bootstrap
  *   cmux       sel ? c1 : c0 = NAND(NAND(c0, NOT sel), NAND(c1, sel)) (:172-182): three bootstraps, two levels
  *   bootstrap  BinFHEScheme::Bootstrap (:190-218)
  *   func       EvalFunc(x, lut) (:241-337): one bootstrap for a negacyclic LUT, two for a periodic or an arbitrary
@@ -348,10 +350,11 @@ int fhe_hip_unpack_keys(int paramset, int method, const uint8_t* bsk_packed, siz
  * finalize levelises the DAG (inputs level 0; a bootstrapped node one more than its operands' highest level; a
  * NOT the level of its source) and gives every level's nodes one contiguous block of rows in the evaluation's
  * ciphertext pool (inputs first).  Evaluation runs level by level: one prep + blind rotation + key switch over
- * ALL gates of a level, whatever their types, times `count` independent instances, one more such launch for the
- * level's FUNC bootstraps at modulus q and one for those at 2q, then one element-wise launch for its linear nodes
+ * ALL gates of a level, whatever their types (the multi-input gates at p = 4 among them), times `count` independent
+ * instances, one more such launch for the level's FUNC bootstraps at modulus q, one for those at 2q and one per
+ * other plaintext modulus of its multi-input gates, then one element-wise launch for its linear nodes
  * (DESIGN.md §4 "Circuits").
- * Not supported (FHE_HIP_ERR_INVALID_PARAM when added): MAJORITY / AND3 / OR3 / AND4 / OR4 nodes, inputs mod Q.
+ * Not supported: inputs mod Q (every input is a ciphertext mod q of dimension n).
  * Errors: FHE_HIP_ERR_INVALID_PARAM for an unknown id, an unsupported gate code, gate(g, x, x) on the same
  * (node, negation) -- the reference's ct1 == ct2 check (:85-86); gate(AND, x, not x) is accepted -- and any add /
  * mark_output / finalize on a finalized circuit; FHE_HIP_ERR_NOT_INIT for a plan query or an evaluation before
@@ -362,6 +365,18 @@ void fhe_hip_circuit_destroy(fhe_hip_circuit* c);
 int fhe_hip_circuit_add_input(fhe_hip_circuit* c, uint32_t* id);
 int fhe_hip_circuit_add_not(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
 int fhe_hip_circuit_add_gate(fhe_hip_circuit* c, int gate, uint32_t x, uint32_t y, uint32_t* id);
+/* gate = MAJORITY, AND3, OR3, AND4 or OR4 over the k nodes xs, 2 <= k <= 4 for every code (the rule of
+ * fhe_hip_eval_gate_multi_batch; the reference sums the vector it is given), at plaintext modulus ptmod >= 2.  An
+ * operand may be any node; one that resolves to a NOT folds in as a sign flip and q/4, which equals the per-gate
+ * entry fed the EvalNOT of that operand.  Encodings are not type-checked (the reference takes p from ctvector[0]):
+ * the caller owns the plaintext modulus of what it wires together, and only p = 4 nodes compose with 2-input
+ * gates and NOT.  Nodes at ptmod = 4 share the level's gate launch; every other modulus in a level is one more
+ * launch, and any number of moduli may be mixed.  FHE_HIP_ERR_INVALID_PARAM for any other gate code, k out of
+ * range, an unknown id, ptmod < 2, or two operands on one (node, negation) -- the reference's pairwise check
+ * (:136-143); (x, not x, y) is accepted.  2 ptmod > q is only known at evaluation, which refuses with
+ * FHE_HIP_ERR_INVALID_PARAM before anything is touched.  fhe_hip_circuit_add_gate keeps refusing these codes. */
+int fhe_hip_circuit_add_gate_multi(fhe_hip_circuit* c, int gate, const uint32_t* xs, uint32_t k, uint32_t ptmod,
+                                   uint32_t* id);
 int fhe_hip_circuit_add_cmux(fhe_hip_circuit* c, uint32_t c0, uint32_t c1, uint32_t sel, uint32_t* id);
 int fhe_hip_circuit_add_bootstrap(fhe_hip_circuit* c, uint32_t x, uint32_t* id);
 /* lut[len], len a power of two >= 4, every value < len.  FHE_HIP_ERR_INVALID_PARAM otherwise, and when x resolves to
@@ -386,10 +401,16 @@ int fhe_hip_circuit_counts(const fhe_hip_circuit* c, size_t* n_inputs, size_t* n
                            size_t* n_bootstraps);
 /* level 0 .. n_levels (0: the inputs): its number of nodes and the pool row of its first node */
 int fhe_hip_circuit_level(const fhe_hip_circuit* c, size_t level, size_t* width, size_t* first_row);
-/* A level's rows in row order: widths[0..2] its bootstraps by launch class (0 gates and BOOTSTRAP, 1 tables at q,
- * 2 tables at 2q with the first stages first; each class one contiguous block), widths[3] its linear rows.
- * Level 0 holds the inputs (not counted here) and its linear rows. */
+/* A level's rows in row order: widths[0..2] its bootstraps by launch class (0 gates, BOOTSTRAP and the multi-input
+ * gates at p = 4, 1 tables at q, 2 tables at 2q with the first stages first; each class one contiguous block),
+ * widths[3] its linear rows.  Between class 2 and the linear rows lie the gate classes of the other plaintext
+ * moduli (below); fhe_hip_circuit_level's width counts them.  Level 0 holds the inputs (not counted here) and its
+ * linear rows. */
 int fhe_hip_circuit_level_classes(const fhe_hip_circuit* c, size_t level, size_t widths[4]);
+/* The level's gate classes of plaintext moduli other than 4, in row order (ascending modulus): *n_classes pairs
+ * (ptmods[i], widths[i]).  Either array may be NULL; otherwise cap (entries) must hold them. */
+int fhe_hip_circuit_level_gate_classes(const fhe_hip_circuit* c, size_t level, uint32_t* ptmods, size_t* widths,
+                                       size_t cap, size_t* n_classes);
 /* *cls = 0 negacyclic, 1 periodic, 2 arbitrary for a func node, -1 for any other; known as soon as it is added */
 int fhe_hip_circuit_func_class(const fhe_hip_circuit* c, uint32_t id, int* cls);
 /* The distinct test-vector tables launch class cls (1 or 2) holds for a parameter set (host only): *n_tables
@@ -416,6 +437,14 @@ int fhe_hip_eval_circuit_batch_device(fhe_hip_ctx* ctx, const fhe_hip_circuit* c
  * test vector (:535-567) of `gate` at b equals that of ref_gate at b + bshift, because the six 2-input gates
  * differ only in where the half-circle window [q1, q1 + q/2) starts. */
 int fhe_hip_gate_fold(int paramset, int method, int gate, int ref_gate, uint32_t* dbl, uint64_t* bshift, uint64_t* q1);
+/* BootstrapGateCore's window (:535-556) of any gate but CMUX at plaintext modulus ptmod (host only): its start q1,
+ * the value Q/(2 ptmod) + 1 of the test vector, the b the extraction adds (that value for the multi-input gates,
+ * :162; (Q >> 3) + 1 for a 2-input gate whatever ptmod, :118) and bshift_to_and = q1(AND) - q1(gate) mod q.  Every
+ * gate's window is the half circle [q1, q1 + q/2), so the fold above holds for the multi-input gates too; launches
+ * differ only in *value.  MAJORITY at ptmod = 4 equals AND in all four.  FHE_HIP_ERR_INVALID_PARAM for CMUX, an
+ * unknown code, ptmod < 2 or 2 ptmod > q. */
+int fhe_hip_gate_window(int paramset, int method, int gate, uint32_t ptmod, uint64_t* q1, uint64_t* value,
+                        uint64_t* b_const, uint64_t* bshift_to_and);
 
 /* LWEEncryptionScheme::KeySwitch (lwe-pke.cpp:348-372): (N, qKS) -> (n, qKS) */
 int fhe_hip_keyswitch_batch(fhe_hip_ctx* ctx, size_t count, const uint64_t* a, const uint64_t* b, uint64_t* a_out,
