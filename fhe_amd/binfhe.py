@@ -147,6 +147,16 @@ def _setup(L):
     L.fhe_hip_encrypt_large.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, sz, u64, ctypes.c_uint32, vp, vp]
     L.fhe_hip_gate_kernel.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_char_p)]
     L.fhe_hip_copy_keys.argtypes = [vp, vp]
+    L.fhe_hip_pubkeygen.argtypes = [ctypes.c_int, ctypes.c_int, vp, u64, vp, vp]
+    L.fhe_hip_pubkeygen_draws.argtypes = [ctypes.c_int, ctypes.c_int, u64, vp]
+    L.fhe_hip_encrypt_pk.argtypes =[ctypes.c_int, ctypes.c_int, vp, vp, vp, sz, u64, u64, ctypes.c_uint32, vp, vp]
+    L.fhe_hip_encrypt_pk_draws.argtypes = [ctypes.c_int, ctypes.c_int, sz, u64, u64, vp, vp, vp]
+    L.fhe_hip_load_pubkey.argtypes = [vp, vp, vp]
+    L.fhe_hip_pubkeygen_device.argtypes = [vp, vp, sz, u64, vp, vp]
+    L.fhe_hip_encrypt_pk_batch.argtypes = [vp, vp, sz, u64, u64, ctypes.c_uint32, ctypes.c_int, vp, vp]
+    L.fhe_hip_encrypt_pk_batch_device.argtypes = [vp, vp, sz, u64, u64, ctypes.c_uint32, ctypes.c_int, vp, vp, vp]
+    L.fhe_hip_encrypt_pk_tile.argtypes = []
+    L.fhe_hip_encrypt_pk_tile.restype = ctypes.c_uint32
     u32, pu32, psz = ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)
     L.fhe_hip_circuit_create.argtypes = [ctypes.POINTER(vp)]
     L.fhe_hip_circuit_destroy.argtypes = [vp]
@@ -281,6 +291,47 @@ def encrypt_large(paramset, method, skN, bits, seed, p=4):
     b = np.zeros(len(bits), np.uint64)
     check(L().fhe_hip_encrypt_large(paramset, method, ptr(_u64(skN)), ptr(bits), len(bits), seed, p, ptr(a), ptr(b)))
     return a, b
+
+
+def pubkeygen(paramset, method, skN, seed):
+    """PubKeyGen (lwe-pke.cpp:74-98) for the ring secret skN (mod qKS, as keygen_ring_secret returns it):
+    (A [N][N], v [N]) mod Q, v[j] = e_j + <A[j], s>"""
+    N = params(paramset, method).N
+    A, v = np.zeros((N, N), np.uint64), np.zeros(N, np.uint64)
+    check(L().fhe_hip_pubkeygen(paramset, method, ptr(_u64(skN)), seed, ptr(A), ptr(v)))
+    return A, v
+
+
+def pubkeygen_draws(paramset, method, seed):
+    """the signed errors e [N] of pubkeygen(.., seed)"""
+    e = np.zeros(params(paramset, method).N, np.int64)
+    check(L().fhe_hip_pubkeygen_draws(paramset, method, seed, ptr(e)))
+    return e
+
+
+def encrypt_pk(paramset, method, A, v, bits, seed, p=4, first=0):
+    """EncryptN (lwe-pke.cpp:133-167) on the host: a [count][N], b [count] mod Q; ciphertext g is a function of
+    (seed, first + g) only"""
+    N = params(paramset, method).N
+    bits = np.ascontiguousarray(bits, dtype=np.int32)
+    a, b = np.zeros((len(bits), N), np.uint64), np.zeros(len(bits), np.uint64)
+    check(L().fhe_hip_encrypt_pk(paramset, method, ptr(_u64(A)), ptr(_u64(v)), ptr(bits), len(bits), first, seed, p,
+                                 ptr(a), ptr(b)))
+    return a, b
+
+
+def encrypt_pk_draws(paramset, method, count, seed, first=0):
+    """the signed draws (s' [count][N], e' [count][N], e'' [count]) of encrypt_pk's ciphertexts
+    [first, first + count)"""
+    N = params(paramset, method).N
+    sp, ep, epp = np.zeros((count, N), np.int64), np.zeros((count, N), np.int64), np.zeros(count, np.int64)
+    check(L().fhe_hip_encrypt_pk_draws(paramset, method, count, first, seed, ptr(sp), ptr(ep), ptr(epp)))
+    return sp, ep, epp
+
+
+def encrypt_pk_tile():
+    """ciphertexts per workgroup of the device EncryptN kernel"""
+    return int(L().fhe_hip_encrypt_pk_tile())
 
 
 def decrypt(paramset, method, sk, a, b, mod=None, p=4):
@@ -688,6 +739,40 @@ class GateEngine:
         check(L().fhe_hip_btkeygen_device(self._h, ptr(sk), sk.size, seed, None, None, None))
         return None
 
+    def load_pubkey(self, A, v):
+        """the public key (A [N][N], v [N] mod Q) made resident (fhe_hip_load_pubkey)"""
+        A, v = _u64(A), _u64(v)
+        N = self.params.N
+        if A.shape != (N, N) or v.shape != (N,):
+            raise FheHipError(-2, "public key: A [N][N] and v [N] expected")
+        check(L().fhe_hip_load_pubkey(self._h, ptr(A), ptr(v)))
+
+    def pubkeygen_device(self, skN, seed, export=False):
+        """PubKeyGen on this engine's device, the key kept resident; identical to pubkeygen(skN, seed).  With
+        export=True (A, v) come back."""
+        skN = _u64(skN)
+        if not export:
+            check(L().fhe_hip_pubkeygen_device(self._h, ptr(skN), skN.size, seed, None, None))
+            return None
+        N = self.params.N
+        A, v = np.zeros((N, N), np.uint64), np.zeros(N, np.uint64)
+        check(L().fhe_hip_pubkeygen_device(self._h, ptr(skN), skN.size, seed, ptr(A), ptr(v)))
+        return A, v
+
+    def encrypt_pk(self, bits, seed, p=4, output=LARGE_DIM, first=0):
+        """Encrypt(pk, m, output, p) of `bits` under the resident public key (fhe_hip_encrypt_pk_batch):
+        LARGE_DIM ([count][N], mod Q) or SMALL_DIM ([count][n], mod q)"""
+        bits = np.ascontiguousarray(bits, dtype=np.int32)
+        a = np.zeros((len(bits), self.params.n if output == SMALL_DIM else self.params.N), np.uint64)
+        b = np.zeros(len(bits), np.uint64)
+        check(L().fhe_hip_encrypt_pk_batch(self._h, ptr(bits), len(bits), first, seed, p, output, ptr(a), ptr(b)))
+        return a, b
+
+    def encrypt_pk_device(self, d_bits, count, seed, d_ao, d_bo, p=4, output=LARGE_DIM, first=0, stream=None):
+        """the same on device buffers (d_bits: int32), asynchronous on stream (fhe_hip_encrypt_pk_batch_device)"""
+        check(L().fhe_hip_encrypt_pk_batch_device(self._h, vp(d_bits), count, first, seed, p, output, vp(d_ao),
+                                                  vp(d_bo), vp(stream) if stream else None))
+
     def eval_gate_packed(self, gate, in1, in2, out_flags=0):
         """EvalBinGate on two PackLWEBatch buffers; returns the packed result."""
         p1, p2 = np.frombuffer(in1, np.uint8), np.frombuffer(in2, np.uint8)
@@ -931,6 +1016,36 @@ class LWEPrivateKey:
     s: np.ndarray  # stored mod qKS, as the reference stores it
 
 
+class LWEPublicKey:
+    """LWEPublicKeyImpl (lwe-publickey.h): A [N][N] and v [N] mod Q.  GetPublicKey() returns one whose arrays
+    stay on the device until A or v is read (they are then regenerated on the host from the key's seed)."""
+
+    def __init__(self, A=None, v=None, _fetch=None):
+        self._A, self._v, self._fetch = A, v, _fetch
+
+    def _get(self):
+        if self._A is None:
+            self._A, self._v = self._fetch()
+        return self._A, self._v
+
+    @property
+    def A(self):
+        return self._get()[0]
+
+    @property
+    def v(self):
+        return self._get()[1]
+
+
+@dataclass
+class LWEKeyPair:
+    publicKey: LWEPublicKey
+    secretKey: LWEPrivateKey
+
+
+SYM_ENCRYPT, PUB_ENCRYPT = 0, 1   # KEYGEN_MODE (binfhe-constants.h)
+
+
 @dataclass
 class SerializedKey:
     """a RingGSWACCKey ("refresh") or LWESwitchingKey stream as Serial::SerializeToFile writes it"""
@@ -1008,10 +1123,48 @@ class BinFHEContext:
     def KeyGen(self):
         return LWEPrivateKey(keygen_secret(self.paramset, self.method, self._next_seed()))
 
-    def BTKeyGen(self, sk):
-        """keys generated on the device (fhe_hip_btkeygen_device); nothing crosses PCIe"""
+    def KeyGenN(self):
+        """KeyGenN (binfhecontext.cpp:203-208): a secret of dimension N (stored mod qKS)"""
+        return LWEPrivateKey(keygen_ring_secret(self.paramset, self.method, self._next_seed()))
+
+    def PubKeyGen(self, skN):
+        """PubKeyGen (binfhecontext.cpp:214-218, lwe-pke.cpp:74-98) of a dimension-N secret"""
+        return LWEPublicKey(*pubkeygen(self.paramset, self.method, skN.s, self._next_seed()))
+
+    def KeyGenPair(self):
+        """KeyGenPair (binfhecontext.cpp:210-212, lwe-pke.cpp:59-71)"""
+        skN = self.KeyGenN()
+        return LWEKeyPair(self.PubKeyGen(skN), skN)
+
+    def BTKeyGen(self, sk, keygenMode=SYM_ENCRYPT):
+        """keys generated on the device (fhe_hip_btkeygen_device); nothing crosses PCIe.  PUB_ENCRYPT
+        (binfhe-base-scheme.cpp:53-57): also the public key of the keys' RLWE secret, generated on the device
+        and kept resident (GetPublicKey)"""
         self._key_seed = self._next_seed()
         self.engine.keygen_device(sk.s, self._key_seed)
+        self._pk = None
+        if keygenMode == PUB_ENCRYPT:
+            ps, m, seed = self.paramset, self.method, self._key_seed
+            self.engine.pubkeygen_device(keygen_ring_secret(ps, m, seed), seed)
+            self._pk = LWEPublicKey(_fetch=lambda: pubkeygen(ps, m, keygen_ring_secret(ps, m, seed), seed))
+            self._resident_pk = self._pk
+
+    def GetPublicKey(self):
+        """the public key BTKeyGen(sk, PUB_ENCRYPT) made (binfhecontext.h GetPublicKey): a handle to the key
+        resident on the device"""
+        if getattr(self, "_pk", None) is None:
+            raise FheHipError(-11, "GetPublicKey needs BTKeyGen(sk, PUB_ENCRYPT)")
+        return self._pk
+
+    def _use_pk(self, pk):
+        if getattr(self, "_resident_pk", None) is not pk:
+            self.engine.load_pubkey(pk.A, pk.v)
+            self._resident_pk = pk
+
+    def EncryptBatch(self, pk, ms, output=SMALL_DIM, p=4):
+        """Encrypt(pk, m, output, p) of every m of ms on the device: arrays (a [count][n or N], b [count])"""
+        self._use_pk(pk)
+        return self.engine.encrypt_pk(ms, self._next_seed(), p, output)
 
     def BTKeyLoad(self, bsk, kskA, kskB=None):
         """raw arrays (bsk, kskA, kskB), or the deserialized refresh / switching keys
@@ -1028,9 +1181,16 @@ class BinFHEContext:
         """Encrypt(sk, m, SMALL_DIM, p, mod) (binfhecontext.cpp:220-234).  output = LARGE_DIM: a
         dimension-N ciphertext mod Q like the one Encrypt(pk, m, LARGE_DIM, p) makes (:236-252), under the RLWE
         secret of the keys BTKeyGen generated (refused after BTKeyLoad: the loaded keys' secret is unknown).
-        The reference's LARGE_DIM encryption is public-key (EncryptN); this one is symmetric under that
-        secret, so it decrypts and bootstraps the same but its noise distribution is not the reference's
-        (parity of the distribution is unpinned; outputs of gates on it are pinned by tests/test_mixed.py)"""
+        With a private key this LARGE_DIM form is symmetric under that secret, so it decrypts and bootstraps
+        like the reference's but its noise distribution is not EncryptN's (outputs of gates on it are pinned by
+        tests/test_mixed.py).
+        Encrypt(pk, m, output = SMALL_DIM, p) with an LWEPublicKey is the reference's public-key form
+        (binfhecontext.cpp:236-252): EncryptN (lwe-pke.cpp:133-167) on the device, mod Q and of dimension N for
+        LARGE_DIM, switched to (n, q) for SMALL_DIM."""
+        if isinstance(sk, LWEPublicKey):
+            out = SMALL_DIM if output is None else output
+            a, b = self.EncryptBatch(sk, [int(m)], out, p)
+            return LWECiphertext(a[0], int(b[0]), self.params.Q if out == LARGE_DIM else self.params.q, p)
         if output == LARGE_DIM:
             if getattr(self, "_key_seed", None) is None:
                 raise FheHipError(-11, "LARGE_DIM encryption needs the keys of BTKeyGen")

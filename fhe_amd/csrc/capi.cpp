@@ -18,6 +18,7 @@
 #include "ntt.h"
 #include "nt.h"
 #include "boot.h"
+#include "pke.h"
 
 using namespace fhe_amd;
 
@@ -1106,6 +1107,78 @@ int fhe_hip_encrypt_large(int paramset, int method, const uint64_t* skN, const i
         return FHE_HIP_OK;
     });
 }
+
+// ---- public-key encryption (keygen.cpp pubkey_gen / encrypt_pk, pke.hip, pke_engine.cpp) ----
+int fhe_hip_pubkeygen(int paramset, int method, const uint64_t* skN, uint64_t seed, uint64_t* A, uint64_t* v) {
+    if (!skN || !A || !v) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        pubkey_gen(make_params(paramset, method), skN, seed, A, v);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_pubkeygen_draws(int paramset, int method, uint64_t seed, int64_t* e) {
+    if (!e) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        pubkey_gen_draws(make_params(paramset, method), seed, e);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_encrypt_pk(int paramset, int method, const uint64_t* A, const uint64_t* v, const int* bits, size_t count,
+                       uint64_t first, uint64_t seed, uint32_t ptmod, uint64_t* a, uint64_t* b) {
+    if (!A || !v || (count && (!bits || !a || !b))) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        encrypt_pk(make_params(paramset, method), A, v, bits, count, first, seed, ptmod, a, b);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_encrypt_pk_draws(int paramset, int method, size_t count, uint64_t first, uint64_t seed, int64_t* sp,
+                             int64_t* ep, int64_t* epp) {
+    if (count && (!sp || !ep || !epp)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        encrypt_pk_draws(make_params(paramset, method), count, first, seed, sp, ep, epp);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_load_pubkey(fhe_hip_ctx* ctx, const uint64_t* A, const uint64_t* v) {
+    if (!ctx || !A || !v) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int { ctx->eng.load_pubkey(A, v); return FHE_HIP_OK; });
+}
+
+int fhe_hip_pubkeygen_device(fhe_hip_ctx* ctx, const uint64_t* skN, size_t N, uint64_t seed, uint64_t* A_out,
+                             uint64_t* v_out) {
+    if (!ctx || !skN) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        ctx_stream(ctx, nullptr);
+        ctx->eng.pubkeygen_device(skN, N, seed, A_out, v_out);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_encrypt_pk_batch(fhe_hip_ctx* ctx, const int* bits, size_t count, uint64_t first, uint64_t seed,
+                             uint32_t ptmod, int output, uint64_t* a_out, uint64_t* b_out) {
+    if (!ctx || (count && (!bits || !a_out || !b_out))) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        ctx_stream(ctx, nullptr);
+        ctx->eng.encrypt_pk_host(bits, count, first, seed, ptmod, output, a_out, b_out);
+        return FHE_HIP_OK;
+    });
+}
+
+int fhe_hip_encrypt_pk_batch_device(fhe_hip_ctx* ctx, const int* d_bits, size_t count, uint64_t first, uint64_t seed,
+                                    uint32_t ptmod, int output, uint64_t* d_a_out, uint64_t* d_b_out, void* stream) {
+    if (!ctx || (count && (!d_bits || !d_a_out || !d_b_out))) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    return guarded([&]() -> int {
+        const CallOrder order(ctx, stream);
+        ctx->eng.encrypt_pk_device(d_bits, count, first, seed, ptmod, output, d_a_out, d_b_out, order.s);
+        return FHE_HIP_OK;
+    });
+}
+
+uint32_t fhe_hip_encrypt_pk_tile(void) { return kPkTileG; }
 
 // ---- boolean circuits (circuit.h, circuit_engine.cpp) ----
 int fhe_hip_circuit_create(fhe_hip_circuit** out) {

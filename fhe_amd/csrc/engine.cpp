@@ -397,7 +397,7 @@ Engine::~Engine() {
                       (void*)d_cdesc_, (void*)d_cio_, (void*)d_tvbuf_, (void*)d_fb_, (void*)d_logGen_, (void*)d_ops_, (void*)d_nops_,
                       d_wtables_, (void*)d_wksk_, (void*)d_wext_a_, (void*)d_wext_b_,
                       (void*)d_epk_, (void*)d_epops_, (void*)d_epn_, d_bsk2_, (void*)d_kspart_, d_tables2k_,
-                      (void*)d_ksk32_})
+                      (void*)d_ksk32_, d_pk_, (void*)d_pkw_, (void*)d_pkio_})
         if (ptr) (void)hipFree(ptr);
     if (order_ev_) (void)hipEventDestroy(order_ev_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -836,6 +836,7 @@ void Engine::copy_keys_from(const Engine& src) {
     k = d_wksk_;
     dup(k, src.d_wksk_);
     d_wksk_ = static_cast<uint64_t*>(k);
+    dup(d_pk_, src.d_pk_);  // the public key, when the source holds one
     FHE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 

@@ -164,6 +164,23 @@ public:
                          bool extended);
     void switch_to_qn_host(size_t count, const uint64_t* a, const uint64_t* b, uint64_t* a_out, uint64_t* b_out);
 
+    // ---- public-key encryption (lwe-pke.cpp:59-98, 133-167; binfhecontext.cpp:236-252); pke.hip ----
+    // the public key (A [N][N], v [N] mod Q, keygen.h pubkey_gen's layout) made resident
+    void load_pubkey(const uint64_t* A, const uint64_t* v);
+    // PubKeyGen on this device: the key pubkey_gen(skN, seed) makes, generated into the resident layout; non-null
+    // host pointers receive A and v
+    void pubkeygen_device(const uint64_t* skN, size_t N, uint64_t seed, uint64_t* A_out, uint64_t* v_out);
+    bool has_pubkey() const { return d_pk_ != nullptr; }
+    // EncryptN of d_bits [count] (int32 messages mod ptmod) as ciphertexts [first, first + count) of stream seed
+    // (keygen.h encrypt_pk, bit for bit).  output 3 (LARGE_DIM): a_out [count][N], b_out [count] mod Q;
+    // 4 (SMALL_DIM): SwitchCTtoqn of those, [count][n] / [count] mod q.  Device pointers, asynchronous on s.
+    static constexpr int kLargeDim = 3, kSmallDim = 4;
+    void encrypt_pk_device(const int32_t* d_bits, size_t count, uint64_t first, uint64_t seed, uint32_t ptmod,
+                           int output, uint64_t* a_out, uint64_t* b_out, hipStream_t s);
+    // the same on host buffers (synchronous)
+    void encrypt_pk_host(const int* bits, size_t count, uint64_t first, uint64_t seed, uint32_t ptmod, int output,
+                         uint64_t* a_out, uint64_t* b_out);
+
     // ---- functional bootstrapping (binfhe-base-scheme.cpp:241-521, 589-648); fb.cpp ----
     // BootstrapFunc: a [count][n] mod ctmod (power of two <= 2N), f[x] = f(x) < fmod for x < ctmod;
     // output [count][n] mod fmod
@@ -329,6 +346,12 @@ private:
     size_t mixcap_ = 0, mixiocap_ = 0;
     uint64_t* d_mix_ = nullptr;
     uint64_t* d_mixio_ = nullptr;
+    // public-key encryption: the resident key (pke.h pk_key_bytes), the packed ternary draws and SMALL_DIM's
+    // dimension-N ciphertexts (pkcap_: bytes), the host entry point's staging (pkiocap_)
+    void* d_pk_ = nullptr;
+    size_t pkcap_ = 0, pkiocap_ = 0;
+    uint64_t* d_pkw_ = nullptr;
+    uint64_t* d_pkio_ = nullptr;
     // functional bootstrapping: test-vector table [2N] u32 and ciphertext temporaries
     uint64_t* d_tvbuf_ = nullptr;   // BootstrapFunc tables: u32 words (u64 on the wide path), grown with their count
     size_t tvcap_ = 0;

@@ -280,6 +280,100 @@ void encrypt(const Params& p, const uint64_t* sk, const int* bits, size_t count,
     }
 }
 
+void ring_secret_signed(const Params& p, const uint64_t* skN, std::vector<int32_t>& s) {
+    s.resize(p.N);
+    for (uint32_t i = 0; i < p.N; ++i) {
+        if (skN[i] >= p.qKS) throw std::invalid_argument("ring secret not reduced mod qKS");
+        const int64_t v = signed_of(skN[i], p.qKS);
+        if (v > kDggMaxFin || v < -kDggMaxFin) throw std::invalid_argument("ring secret entry out of range");
+        s[i] = (int32_t)v;
+    }
+}
+
+void pubkey_gen_draws(const Params& p, uint64_t seed, int64_t* e) {
+    Rng r(seed, T_PKV, 0);
+    for (uint32_t j = 0; j < p.N; ++j) e[j] = r.dgg();
+}
+
+void pubkey_gen(const Params& p, const uint64_t* skN, uint64_t seed, uint64_t* A, uint64_t* v) {
+    const uint32_t N = p.N;
+    const uint64_t Q = p.Q;
+    std::vector<int32_t> s;
+    ring_secret_signed(p, skN, s);
+    std::vector<uint64_t> sq(N);
+    for (uint32_t i = 0; i < N; ++i) sq[i] = lift(s[i], Q);
+    std::vector<int64_t> e(N);
+    pubkey_gen_draws(p, seed, e.data());
+    for (uint32_t j = 0; j < N; ++j) v[j] = lift(e[j], Q);
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < (int64_t)N; ++j) {
+        Rng r(seed, T_PKA, (uint64_t)j);
+        uint64_t* row = A + (size_t)j * N;
+        uint64_t acc = v[j];
+        for (uint32_t i = 0; i < N; ++i) {
+            row[i] = r.uniform(Q);
+            acc = addmod(acc, mulmod(row[i], sq[i], Q), Q);
+        }
+        v[j] = acc;
+    }
+}
+
+void encrypt_pk_draws(const Params& p, size_t count, uint64_t first, uint64_t seed, int64_t* sp, int64_t* ep,
+                      int64_t* epp) {
+    const uint32_t N = p.N;
+    for (size_t g = 0; g < count; ++g) {
+        Rng r(seed, T_PKENC, first + g);
+        for (uint32_t j = 0; j < N; ++j) sp[g * N + j] = r.ternary();
+        for (uint32_t i = 0; i < N; ++i) ep[g * N + i] = r.dgg();
+        epp[g] = r.dgg();
+    }
+}
+
+void encrypt_pk(const Params& p, const uint64_t* A, const uint64_t* v, const int* bits, size_t count, uint64_t first,
+                uint64_t seed, uint32_t ptmod, uint64_t* a, uint64_t* b) {
+    const uint32_t N = p.N;
+    const uint64_t Q = p.Q;
+    if (ptmod < 2 || ptmod > Q) throw std::invalid_argument("plaintext modulus out of range");
+    for (size_t k = 0; k < (size_t)N * N; ++k)
+        if (A[k] >= Q) throw std::invalid_argument("public key not reduced mod Q");
+    for (uint32_t j = 0; j < N; ++j)
+        if (v[j] >= Q) throw std::invalid_argument("public key not reduced mod Q");
+    const bool lazy = Q < (1ull << 31);  // signed 64-bit sums: N Q < 2^43
+#pragma omp parallel for schedule(dynamic, 1) if (count > 1)
+    for (int64_t g = 0; g < (int64_t)count; ++g) {
+        std::vector<int64_t> sp(N), ep(N);
+        int64_t epp;
+        encrypt_pk_draws(p, 1, first + (uint64_t)g, seed, sp.data(), ep.data(), &epp);
+        uint64_t* ag = a + (size_t)g * N;
+        if (lazy) {
+            for (uint32_t j = 0; j < N; ++j) {
+                const uint64_t* row = A + (size_t)j * N;
+                if (sp[j] > 0)
+                    for (uint32_t i = 0; i < N; ++i) ep[i] += (int64_t)row[i];
+                else if (sp[j] < 0)
+                    for (uint32_t i = 0; i < N; ++i) ep[i] -= (int64_t)row[i];
+            }
+            for (uint32_t i = 0; i < N; ++i) ag[i] = lift(ep[i], Q);
+        } else {
+            for (uint32_t i = 0; i < N; ++i) ag[i] = lift(ep[i], Q);
+            for (uint32_t j = 0; j < N; ++j) {
+                const uint64_t* row = A + (size_t)j * N;
+                if (sp[j] > 0)
+                    for (uint32_t i = 0; i < N; ++i) ag[i] = addmod(ag[i], row[i], Q);
+                else if (sp[j] < 0)
+                    for (uint32_t i = 0; i < N; ++i) ag[i] = submod(ag[i], row[i], Q);
+            }
+        }
+        uint64_t acc = ((uint64_t)((uint32_t)bits[g] % ptmod) * (Q / ptmod)) % Q;
+        acc = addmod(acc, lift(epp, Q), Q);
+        for (uint32_t j = 0; j < N; ++j) {
+            if (sp[j] > 0) acc = addmod(acc, v[j], Q);
+            else if (sp[j] < 0) acc = submod(acc, v[j], Q);
+        }
+        b[g] = acc;
+    }
+}
+
 int64_t decrypt(const Params& p, const uint64_t* sk, const uint64_t* a, uint64_t b, uint32_t len, uint64_t mod,
                 uint32_t ptmod) {
     u128 acc = 0;

@@ -42,7 +42,8 @@ struct KeySet {
 // counter-based generator: stream (seed, tag, stream) yields out_k = mix64(rng_state(..) + (k + 2) * kRngGamma)
 // for its k-th draw, so the device key generation (keygen_dev.hip) reproduces any draw independently.
 // The stream's state is a hash of (seed, tag, stream): nearby seeds give unrelated streams.
-enum RngTag : uint64_t { T_SK = 1, T_SKN, T_BSK, T_KSK, T_ENC, T_AUTO };
+// T_PKA / T_PKV / T_PKENC: the public key's matrix and error, and EncryptN's draws (pubkey_gen / encrypt_pk)
+enum RngTag : uint64_t { T_SK = 1, T_SKN, T_BSK, T_KSK, T_ENC, T_AUTO, T_PKA, T_PKV, T_PKENC };
 constexpr uint64_t kRngGamma = 0x9E3779B97F4A7C15ull;
 FHE_HD inline uint64_t mix64(uint64_t z) {  // splitmix64's finaliser
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -101,5 +102,30 @@ void encrypt(const Params& p, const uint64_t* sk, const int* bits, size_t count,
              uint64_t* b, uint32_t ptmod = 4, uint64_t mod = 0, uint32_t len = 0);
 int64_t decrypt(const Params& p, const uint64_t* sk, const uint64_t* a, uint64_t b, uint32_t len, uint64_t mod,
                 uint32_t ptmod = 4);
+
+// ---- public-key encryption (KeyGenPair / PubKeyGen lwe-pke.cpp:59-98, EncryptN :133-167) ----
+// The signed secret s_i of skN [N] stored mod qKS (as fhe_hip_keygen_ring_secret returns it and decrypt reads
+// it); entries beyond the key distributions' range (|s_i| > kDggMaxFin) are refused.
+void ring_secret_signed(const Params& p, const uint64_t* skN, std::vector<int32_t>& s);
+// PubKeyGen: A [N][N] row-major and v [N], mod Q.
+//   row j of A : stream (seed, T_PKA, j), draws 0 .. N-1, uniform(Q)
+//   e_j        : draw j of stream (seed, T_PKV, 0), dgg_sample
+//   v[j]       = e_j + sum_i A[j][i] s_i mod Q                                   (:90-95)
+void pubkey_gen(const Params& p, const uint64_t* skN, uint64_t seed, uint64_t* A, uint64_t* v);
+// the errors e [N] of pubkey_gen(seed) as signed values
+void pubkey_gen_draws(const Params& p, uint64_t seed, int64_t* e);
+// EncryptN of bits[g] (messages mod ptmod), g < count, with ciphertext modulus Q; ciphertext g uses stream
+// (seed, T_PKENC, first + g) and nothing else, so a batch cut into several calls gives the same ciphertexts:
+//   draws 0 .. N-1  : s'_j = uniform(3) - 1                                      (TernaryUniformGenerator, :144-145)
+//   draws N .. 2N-1 : e'_i = dgg_sample                                          (:149)
+//   draw 2N         : e''                                                        (:158)
+//   a_i = e'_i + sum_j s'_j A[j][i] mod Q                                        (:151-154)
+//   b   = (m mod ptmod) floor(Q / ptmod) + e'' + sum_j v[j] s'_j mod Q           (:158-162)
+// a [count][N], b [count]
+void encrypt_pk(const Params& p, const uint64_t* A, const uint64_t* v, const int* bits, size_t count, uint64_t first,
+                uint64_t seed, uint32_t ptmod, uint64_t* a, uint64_t* b);
+// the draws of ciphertexts [first, first + count) of encrypt_pk as signed values: sp, ep [count][N], epp [count]
+void encrypt_pk_draws(const Params& p, size_t count, uint64_t first, uint64_t seed, int64_t* sp, int64_t* ep,
+                      int64_t* epp);
 
 }  // namespace fhe_amd

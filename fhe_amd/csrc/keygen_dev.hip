@@ -23,6 +23,7 @@
 #include "keygen.h"
 #include "nt.h"
 #include "ntt.h"
+#include "rng_dev.h"
 
 namespace fhe_amd {
 namespace {
@@ -38,16 +39,6 @@ struct KgDesc {
     uint32_t pad;
 };
 static_assert(sizeof(KgDesc) == 40, "descriptor layout");
-
-__device__ __forceinline__ uint64_t draw(uint64_t s0, uint64_t k) { return mix64(s0 + (k + 2) * kRngGamma); }
-__device__ __forceinline__ uint64_t draw_uniform(uint64_t s0, uint64_t k, uint64_t m) {
-    return __umul64hi(draw(s0, k), m);
-}
-// the reference's discrete Gaussian (keygen.h dgg_sample) on the host's table, lifted mod m
-__device__ __forceinline__ uint64_t draw_dgg(uint64_t s0, uint64_t k, uint64_t m, const DggTable& t) {
-    const int64_t v = dgg_sample(draw(s0, k), t);
-    return v < 0 ? (uint64_t)(v + (int64_t)m) : (uint64_t)v;
-}
 
 __global__ void __launch_bounds__(256) k_kg_sample(const KgDesc* __restrict__ D, uint32_t N, uint64_t Q,
                                                    uint64_t* __restrict__ A, uint64_t* __restrict__ T, DggTable dg) {

@@ -126,7 +126,7 @@ int fhe_hip_load_bsk(fhe_hip_ctx* ctx, const uint64_t* bsk, size_t n_words);
 int fhe_hip_load_ksk(fhe_hip_ctx* ctx, const uint64_t* A, size_t nA, const uint64_t* B, size_t nB);
 /* The resident keys of src (same parameter set and method, any device) into dst: device-to-device copies of
  * the packed key buffers (xGMI peer copies between GPUs), no host repacking -- the per-device key fan-out of
- * fhe_hip_multi_load_keys */
+ * fhe_hip_multi_load_keys; a resident public key (fhe_hip_load_pubkey / fhe_hip_pubkeygen_device) is copied too */
 int fhe_hip_copy_keys(fhe_hip_ctx* dst, const fhe_hip_ctx* src);
 /* BTKeyGen on the context's device (BinFHEContext::BTKeyGen binfhecontext.cpp:185-200 -> KeyGenAcc
  * rgsw-acc-cggi.cpp:39-96 / rgsw-acc-dm.cpp:39-114 / rgsw-acc-lmkcdey.cpp:39-226, KeySwitchGen
@@ -492,9 +492,53 @@ int fhe_hip_decrypt_ptmod(int paramset, int method, const uint64_t* sk, const ui
  * fhe_hip_decrypt_ptmod with len = N, mod = Q decrypts them under it. */
 int fhe_hip_keygen_ring_secret(int paramset, int method, uint64_t seed, uint64_t* skN);
 /* Encrypt(pk, m, LARGE_DIM, p) (binfhecontext.cpp:236-252, EncryptN): a[count][N], b[count] mod Q under skN
- * (a symmetric encryption under the key the public key belongs to; uniform a, the reference's Gaussian) */
+ * (a symmetric encryption under the key the public key belongs to; uniform a, the reference's Gaussian; the
+ * public-key form itself is fhe_hip_encrypt_pk below) */
 int fhe_hip_encrypt_large(int paramset, int method, const uint64_t* skN, const int* bits, size_t count, uint64_t seed,
                           uint32_t ptmod, uint64_t* a, uint64_t* b);
+
+/* ------------------------------------------------------------------------ */
+/* Public-key encryption (KeyGenPair / PubKeyGen lwe-pke.cpp:59-98, EncryptN */
+/*   lwe-pke.cpp:133-167, Encrypt(pk, ..) binfhecontext.cpp:236-252)         */
+/* ------------------------------------------------------------------------ */
+/* PubKeyGen (lwe-pke.cpp:74-98) for the ring secret skN[N] (mod qKS, as fhe_hip_keygen_ring_secret returns it):
+ * A[N][N] row-major uniform mod Q, v[j] = e_j + <A[j], s> mod Q.  With skN = fhe_hip_keygen_ring_secret(seed) the
+ * key belongs to the keys fhe_hip_keygen / fhe_hip_btkeygen_device make from that seed (with timeOptimization: to
+ * the key of the context's own baseG, as m_BTKey.Pkey does, binfhe-base-scheme.cpp:53-57). */
+int fhe_hip_pubkeygen(int paramset, int method, const uint64_t* skN, uint64_t seed, uint64_t* A, uint64_t* v);
+/* the errors e[N] of fhe_hip_pubkeygen(seed) as signed values (draw j of its error stream) */
+int fhe_hip_pubkeygen_draws(int paramset, int method, uint64_t seed, int64_t* e);
+/* EncryptN (lwe-pke.cpp:133-167) with ciphertext modulus Q: a[count][N], b[count];
+ * a_i = e'_i + sum_j s'_j A[j][i] (:151-154), b = (m mod ptmod) floor(Q / ptmod) + e'' + sum_j v[j] s'_j (:158-162),
+ * s' uniform ternary.  Ciphertext g depends on (seed, first + g) only: a batch cut into several calls, or sharded
+ * over devices, gives the same ciphertexts.  FHE_HIP_ERR_INVALID_PARAM for ptmod < 2 or ptmod > Q. */
+int fhe_hip_encrypt_pk(int paramset, int method, const uint64_t* A, const uint64_t* v, const int* bits, size_t count,
+                       uint64_t first, uint64_t seed, uint32_t ptmod, uint64_t* a, uint64_t* b);
+/* The draws of ciphertexts [first, first + count) of fhe_hip_encrypt_pk as signed values: sp[count][N] (s'),
+ * ep[count][N] (e'), epp[count] (e'') */
+int fhe_hip_encrypt_pk_draws(int paramset, int method, size_t count, uint64_t first, uint64_t seed, int64_t* sp,
+                             int64_t* ep, int64_t* epp);
+/* The public key made resident on the context's device (A[N][N], v[N], reduced mod Q) */
+int fhe_hip_load_pubkey(fhe_hip_ctx* ctx, const uint64_t* A, const uint64_t* v);
+/* PubKeyGen on the device: the key fhe_hip_pubkeygen(skN, seed) makes, bit for bit, generated in place in the
+ * resident layout; A_out / v_out (either may be NULL) receive it.  N must be the set's ring dimension. */
+int fhe_hip_pubkeygen_device(fhe_hip_ctx* ctx, const uint64_t* skN, size_t N, uint64_t seed, uint64_t* A_out,
+                             uint64_t* v_out);
+/* Encrypt(pk, m, output, p) (binfhecontext.cpp:236-252) of bits[count] under the resident public key, the
+ * ciphertexts fhe_hip_encrypt_pk makes for (first, seed), bit for bit.  output 3 (LARGE_DIM): a_out[count][N],
+ * b_out[count] mod Q, the row layout fhe_hip_eval_mixed_batch reads as "large"; 4 (SMALL_DIM): SwitchCTtoqn of
+ * those (:246-249), a_out[count][n], b_out[count] mod q.  FHE_HIP_ERR_INVALID_PARAM for ptmod < 2, ptmod > Q or
+ * another output; FHE_HIP_ERR_NOT_INIT without a resident public key (SMALL_DIM: or switching key); count = 0
+ * is a no-op. */
+#define FHE_HIP_LARGE_DIM 3
+#define FHE_HIP_SMALL_DIM 4
+int fhe_hip_encrypt_pk_batch(fhe_hip_ctx* ctx, const int* bits, size_t count, uint64_t first, uint64_t seed,
+                             uint32_t ptmod, int output, uint64_t* a_out, uint64_t* b_out);
+/* The same on device buffers (d_bits: int32), asynchronous on stream and ordered with the context's other calls */
+int fhe_hip_encrypt_pk_batch_device(fhe_hip_ctx* ctx, const int* d_bits, size_t count, uint64_t first, uint64_t seed,
+                                    uint32_t ptmod, int output, uint64_t* d_a_out, uint64_t* d_b_out, void* stream);
+/* ciphertexts per workgroup of the EncryptN kernel (batch sizes around its multiples are the tile edges) */
+uint32_t fhe_hip_encrypt_pk_tile(void);
 
 /* ------------------------------------------------------------------------ */
 /* Device memory (Backend::Allocate/Free/CopyToDevice/CopyToHost/Synchronize, */
