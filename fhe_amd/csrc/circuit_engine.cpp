@@ -52,14 +52,14 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
     }
     // the pool: every node's B ciphertexts, no row reuse; refused when it would not fit
     const size_t pool_bytes = rows * B * (n + 1) * 8;
-    if (pool_bytes > poolcap_) {
+    if (pool_bytes > pool_.bytes()) {
         size_t fr = 0, tot = 0;
         FHE_HIP_CHECK(hipMemGetInfo(&fr, &tot));
-        if (pool_bytes > fr + poolcap_)
+        if (pool_bytes > fr + pool_.bytes())
             throw AllocError("circuit: a pool of " + std::to_string(pool_bytes) + " bytes exceeds the device's free memory (" +
                              std::to_string(fr) + " bytes)");
     }
-    uint64_t* pool_a = grow(d_pool_, poolcap_, pool_bytes);
+    uint64_t* pool_a = reserve(pool_, pool_bytes);
     uint64_t* pool_b = pool_a + rows * B * n;
     if (widest) ensure_work(std::min(widest, chunk));
 
@@ -68,7 +68,7 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
     // rounded up to 8 bytes: slots, outputs, LINEAR rows, class-1 tables, class-2 tables (u32 words, u64 on the
     // wide path, already scaled by Q / fmod).
     auto up8 = [](size_t x) { return (x + 7) / 8 * 8; };
-    const size_t n_slots = c.num_bootstraps(), n_lin = c.num_linears(), tw = wide_ ? 8 : 4;
+    const size_t n_slots = c.num_bootstraps(), n_lin = c.num_linears(), tw = flags_.wide ? 8 : 4;
     const size_t desc_bytes = up8(n_slots * sizeof(CircuitSlot));
     const size_t lin_off = desc_bytes + up8(n_out * sizeof(CircuitOut));
     const size_t tab_off[3] = {0, lin_off + up8(n_lin * sizeof(CircuitLinear)),
@@ -80,8 +80,7 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         const std::vector<CircuitLinear> lins = c.linears(p_);
         sync_streams();  // the previous circuit's kernels may still read the old descriptors
         cdesc_serial_ = 0;
-        grow(d_cdesc_, cdesccap_, all_bytes);
-        char* base = reinterpret_cast<char*>(d_cdesc_);
+        char* base = reinterpret_cast<char*>(reserve(cdesc_, all_bytes));
         if (n_slots) FHE_HIP_CHECK(hipMemcpy(base, slots.data(), n_slots * sizeof(CircuitSlot), hipMemcpyHostToDevice));
         if (n_out)
             FHE_HIP_CHECK(hipMemcpy(base + desc_bytes, outs.data(), n_out * sizeof(CircuitOut), hipMemcpyHostToDevice));
@@ -89,7 +88,7 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         for (int cls = 1; cls <= 2; ++cls) {
             if (!c.num_tables(cls)) continue;
             const std::vector<uint64_t> tv = c.tables(p_, cls);
-            if (wide_) {
+            if (flags_.wide) {
                 FHE_HIP_CHECK(hipMemcpy(base + tab_off[cls], tv.data(), tv.size() * 8, hipMemcpyHostToDevice));
             } else {
                 const std::vector<uint32_t> tv32(tv.begin(), tv.end());
@@ -98,7 +97,7 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         }
         cdesc_serial_ = c.serial();
     }
-    const char* dbase = reinterpret_cast<const char*>(d_cdesc_);
+    const char* dbase = cdesc_.as<const char>();
     const CircuitSlot* d_slots = reinterpret_cast<const CircuitSlot*>(dbase);
     const CircuitOut* d_outs = reinterpret_cast<const CircuitOut*>(dbase + desc_bytes);
     const CircuitLinear* d_lins = reinterpret_cast<const CircuitLinear*>(dbase + lin_off);
@@ -117,8 +116,8 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
         g.qKS = p_.qKS;
         g.ctmod = cls == 1 ? cm1 : cm2;
         g.factor = 2 * p_.N / g.ctmod;
-        g.tv = wide_ ? nullptr : reinterpret_cast<const uint32_t*>(dbase + tab_off[cls]);
-        g.tv64 = wide_ ? reinterpret_cast<const uint64_t*>(dbase + tab_off[cls]) : nullptr;
+        g.tv = flags_.wide ? nullptr : reinterpret_cast<const uint32_t*>(dbase + tab_off[cls]);
+        g.tv64 = flags_.wide ? reinterpret_cast<const uint64_t*>(dbase + tab_off[cls]) : nullptr;
         g.tv_mod = 0;   // the table comes per slot, in the high half of tvb
         g.b_const = 0;  // ctExt = (acc0, acc1[0]) (binfhe-base-scheme.cpp:624-626)
         g.msb_out = 1;
@@ -172,31 +171,6 @@ void Engine::eval_circuit_device(const Circuit& c, size_t B, const uint64_t* a_i
     }
     if (n_out)
         FHE_HIP_CHECK(launch_circuit_gather(pool_a, pool_b, d_outs, (uint32_t)n_out, (uint32_t)B, p_.n, p_.q, a_out, b_out, s));
-}
-
-void Engine::eval_circuit_host(const Circuit& c, size_t B, const uint64_t* a_in, const uint64_t* b_in, uint64_t* a_out,
-                               uint64_t* b_out) {
-    if (!c.finalized()) throw std::logic_error("circuit is not finalized");
-    if (B == 0) return;
-    const size_t n = p_.n, n_in = c.num_inputs(), n_out = c.num_outputs();
-    if ((n_in && (!a_in || !b_in)) || (n_out && (!a_out || !b_out))) throw std::invalid_argument("null argument");
-    if (B > 0x7fffffffull || c.num_rows() * B > 0x7fffffffull) throw std::invalid_argument("batch too large");
-    FHE_HIP_CHECK(hipSetDevice(device_));
-    uint64_t* d = grow(d_cio_, ciocap_, (n_in + n_out) * B * (n + 1) * 8 + 8);
-    uint64_t* dai = d;
-    uint64_t* dbi = dai + n_in * B * n;
-    uint64_t* dao = dbi + n_in * B;
-    uint64_t* dbo = dao + n_out * B * n;
-    if (n_in) {
-        FHE_HIP_CHECK(hipMemcpyAsync(dai, a_in, n_in * B * n * 8, hipMemcpyHostToDevice, stream_));
-        FHE_HIP_CHECK(hipMemcpyAsync(dbi, b_in, n_in * B * 8, hipMemcpyHostToDevice, stream_));
-    }
-    eval_circuit_device(c, B, dai, dbi, dao, dbo, stream_);
-    if (n_out) {
-        FHE_HIP_CHECK(hipMemcpyAsync(a_out, dao, n_out * B * n * 8, hipMemcpyDeviceToHost, stream_));
-        FHE_HIP_CHECK(hipMemcpyAsync(b_out, dbo, n_out * B * 8, hipMemcpyDeviceToHost, stream_));
-    }
-    FHE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 }  // namespace fhe_amd

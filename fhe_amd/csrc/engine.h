@@ -18,24 +18,39 @@
 
 #include "boot.h"
 #include "boot_wide.h"
+#include "devbuf.h"
 #include "params.h"
 
 namespace fhe_amd {
 
-struct HipError : std::runtime_error {
-    hipError_t code;
-    HipError(hipError_t e, const std::string& what)
-        : std::runtime_error(what + ": " + hipGetErrorString(e)), code(e) {}
-};
 // a device workspace that would not fit the device's free memory (FHE_HIP_ERR_ALLOC)
 struct AllocError : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
-#define FHE_HIP_CHECK(expr)                                   \
-    do {                                                      \
-        hipError_t _e = (expr);                               \
-        if (_e != hipSuccess) throw HipError(_e, #expr);      \
-    } while (0)
+
+// Which accumulator kernels a parameter set runs on, from the static predicates and the A/B knobs of the
+// environment (kernel_flags is the only reader of FHE_HIP_NARROW / GINX3 / N2K / KS32 / GINX_KERNEL / LMK_KERNEL)
+struct KernelFlags {
+    bool wide = false;    // the 64-bit path (boot_wide.h): every set outside fast_path
+    bool narrow = false;  // its accumulator in 32-bit residues (A32)
+    bool g3 = false;      // digitsG = 4 at N = 1024 on the split kernels (K1s-3 / K1m-3)
+    bool n2k = false;     // N = 2048 on K1w
+    bool ks32 = false;    // the 64-bit path's key switch on the u16-row tiled kernel
+    bool ks32w = false;   // ... on its u32-sum form
+    int ginx_pin = 0;     // FHE_HIP_GINX_KERNEL: 0 by batch size, 1 wave, 2 split, 3 xsplit, 4 qsplit
+    int lmk_pin = 0;      // FHE_HIP_LMK_KERNEL: 0 by batch size, 1 wave, 2 split, 4 qsplit
+};
+
+// What one blind rotation launches: decided once by Engine::plan_rotation, launched by rotate_device and
+// reported by gate_kernel
+// (the first seven write the u32 ctExt of the 32-bit path, the others the u64 ctExt of the 64-bit path)
+enum class RotKernel { Ginx, Ginx2, Ginx2x, Ginx4x, Lmk, LmkX, Lmk4x, Lmk3, Lmk2k, WideOps, N2k, Ginx3, Wide };
+struct RotationPlan {
+    RotKernel launcher;
+    const char* name;
+    int gw;      // gates per workgroup (K1x / K1m-2)
+    int nd;      // retained digits (K1w / K1s-3)
+};
 
 class Engine {
 public:
@@ -53,10 +68,16 @@ public:
     hipStream_t use_stream(hipStream_t s);
     void end_call(hipStream_t s);
     void sync_streams();  // waits for the context's stream and the last asynchronous call
+    // the staging block of the synchronous host-buffer calls (one call at a time uses it)
+    uint64_t* host_stage(size_t bytes) { return reserve(stage_, bytes); }
     bool ready() const { return d_bsk_ && (d_ksk_ || d_wksk_); }
     // the 64-bit accumulator (boot_wide.h): the large-precision family and the GINX sets outside
     // the 32-bit kernel's range
-    bool wide() const { return wide_; }
+    bool wide() const { return flags_.wide; }
+    // the kernel flags of a parameter set under the current environment, and their fhe_hip_params::kernel code
+    // (0 K5, 1 the 32-bit kernels, 2 split digitsG = 4, 3 K5 in 32-bit residues, 4 K1w)
+    static KernelFlags kernel_flags(const Params& p);
+    static uint32_t kernel_code(const KernelFlags& f);
     // the 32-bit kernels' range: N = 1024, Q < 2^28, digitsG = 3, power-of-two q, qKS <= 2^16, n < 1024
     static bool fast_path(const Params& p);
     static bool narrow_set(const Params& p);  // the 64-bit accumulator runs its 32-bit policy (A32)
@@ -70,9 +91,9 @@ public:
     static bool ks32w_set(const Params& p);
     // the accumulator kernels a context of this set runs on (fhe_hip_params::kernel), with the A/B
     // environment knobs a context reads at creation (FHE_HIP_GINX3, FHE_HIP_N2K, FHE_HIP_NARROW)
-    static uint32_t kernel_kind(const Params& p);
+    static uint32_t kernel_kind(const Params& p) { return kernel_code(kernel_flags(p)); }
     // the same for this context: its own kernel flags, read from the environment when it was created
-    uint32_t kernel() const;
+    uint32_t kernel() const { return kernel_code(flags_); }
     // the blind-rotation kernel a 2-input gate batch of `count` ciphertexts runs on in this context
     const char* gate_kernel(size_t count) const;
 
@@ -229,19 +250,42 @@ public:
                         const uint64_t* a2, const uint64_t* b2, uint64_t* a_out, uint64_t* b_out);
 
 private:
+    using DevBuf = devmem::DevBuf;
+    template <typename T>
+    using DevArr = devmem::DevArr<T>;
     // p: plaintext modulus of the bootstrapped ciphertext; multi: AND3..OR4/MAJORITY allowed
     GateArgs gate_args(int gate, size_t count, uint32_t p = 4, bool multi = false) const;
     // prep of g.count gates into the workspace slots [offset, offset + g.count)
     void prep_device(const GateArgs& g, const GateInputs& in, size_t offset, hipStream_t s);
-    // blind rotation of workspace slots [0, g.count)
+    // Grow-only device scratch: at least `bytes` in b.  Before a block is replaced it waits for the context's
+    // stream, the last finished call's event and the stream of the call in progress, so no kernel enqueued
+    // earlier -- in this call or before it -- still reads the block that is freed.
+    uint64_t* reserve(DevBuf& b, size_t bytes);
+    // the blind-rotation kernel of this launch: the context's flags, the resident key layouts, the method, the
+    // FHE_HIP_GINX_KERNEL / FHE_HIP_LMK_KERNEL pins or the batch size, and whether the split kernels take these
+    // arguments.  Throws where the launch is refused (the 32-bit path's digit range).
+    RotationPlan plan_rotation(const GateArgs& g) const;
+    // blind rotation of workspace slots [0, g.count): plan_rotation's kernel
     void rotate_device(const GateArgs& g, hipStream_t s);
     void fb_floor(size_t count, const uint64_t* a, const uint64_t* b, uint64_t mod, uint32_t roundbits, uint64_t* a_out,
                   uint64_t* b_out, uint64_t* w, hipStream_t s);
-    uint64_t* fb_work(size_t count, int cts);
-    void stage_inputs(size_t count, uint32_t k, const uint64_t* const* a, const uint64_t* const* b,
-                      const uint64_t** da, const uint64_t** db);
+    // functional bootstrapping's temporaries: count x cts ciphertexts of n + 1 words
+    uint64_t* fb_work(size_t count, int cts) { return reserve(fb_, count * (size_t)cts * ((size_t)p_.n + 1) * 8); }
+    // A synchronous host-buffer call: the listed host arrays staged in one block (Carver: one list is its size
+    // and its layout), run(d_in, d_a_out, d_b_out) on the context's stream, the outputs of aw / bw words copied
+    // back, the stream synchronised.  engine_host.cpp.
+    struct HostIn {
+        const void* src;  // nullptr or bytes = 0: the words are reserved, nothing is uploaded
+        size_t words;     // u64 words reserved
+        size_t bytes;     // uploaded
+    };
+    template <typename Run>
+    void host_call(const std::vector<HostIn>& in, size_t aw, size_t bw, uint64_t* a_out, uint64_t* b_out, Run&& run);
+    // the same for k ciphertext columns (a [count][n], b [count]) and outputs [count][n] / [count]
+    template <typename Run>
+    void host_columns(size_t count, uint32_t k, const uint64_t* const* a, const uint64_t* const* b, bool staged_out,
+                      uint64_t* a_out, uint64_t* b_out, Run&& run);
     void ensure_work(size_t count);
-    void ensure_host_stage(size_t count);
     void build_tables();
     void build_tables_wide();
     void build_loggen();
@@ -257,8 +301,6 @@ private:
     void cmux_levels(size_t count, const uint64_t* a0, const uint64_t* b0, const uint64_t* a1, const uint64_t* b1,
                      const uint64_t* a2, const uint64_t* b2, const uint64_t* a2n, const uint64_t* b2n, uint64_t* a_out,
                      uint64_t* b_out, hipStream_t s);
-    // grow-only device scratch (synchronises the context's streams before it grows)
-    uint64_t* grow(uint64_t*& ptr, size_t& cap, size_t bytes);
     // KeySwitch + ModSwitch(qKS -> q_out) of workspace slots [0, count) (q_out = 0: none)
     void keyswitch_ext(size_t count, uint64_t q_out, uint64_t* a_out, uint64_t* b_out, hipStream_t s);
     // ctExt of workspace slots [0, count) to host u64 arrays
@@ -266,120 +308,95 @@ private:
 
     Params p_;
     int device_;
+    KernelFlags flags_;   // kernel_flags(p_) when the context was created
     hipStream_t stream_ = nullptr;
+    // Every device allocation below is a DevBuf: freed by its destructor, after ~Engine has synchronised and
+    // destroyed the stream.  Resident tables and keys are allocated where they are built or loaded; the rest is
+    // grow-only scratch that goes through reserve().
     BootTables tabs_{};
-    void* d_tables_ = nullptr;
-    void* d_bsk_ = nullptr;
-    void* d_autok_ = nullptr;   // LMKCDEY automorphism keys (inside the d_bsk_ allocation)
-    int16_t* d_logGen_ = nullptr;
+    DevArr<void> d_tables_;
+    DevArr<void> d_bsk_;
+    void* d_autok_ = nullptr;   // LMKCDEY automorphism keys (inside the d_bsk_ allocation, not owned)
+    DevArr<int16_t> d_logGen_;
     uint32_t maxops_ = 0;
-    uint16_t* d_ops_ = nullptr;
-    uint32_t* d_nops_ = nullptr;
-    uint16_t* d_ksk_ = nullptr;
-    uint32_t* d_kspart_ = nullptr;   // row-split key-switch partials (ks_part)
+    DevArr<uint16_t> d_ops_;
+    DevArr<uint32_t> d_nops_;
+    DevArr<uint16_t> d_ksk_;
+    DevArr<uint32_t> d_kspart_;   // row-split key-switch partials (ks_part)
     static constexpr size_t kKsPartWords = (size_t)1 << 25;  // 2^16 rows x 512 u32
     uint32_t* ks_part(size_t count);
-    // GINX kernel choice: 0 by batch size, 1 one wave per gate (K1), 2 two waves per gate with the digit
-    // exchange (K1s), 3 two waves per gate with K1w's one-word exchange (K1x).  K1s is slower than K1 at
-    // every batch size (1024 gates 4.87 vs 4.37 ms: two barriers per index, the partner's digits read in
-    // the MAC) and only FHE_HIP_GINX_KERNEL=split pins it; K1x runs batches of up to kXBatch gates.
-    int ginx_kernel_ = 0;
-    // GINX kernel of a gate launch (ginx_kernel_ pins, else by batch size): 1 K1, 2 K1s, 3 K1x, 4 K1q (four waves
-    // per gate, up to one gate per CU; FHE_HIP_GINX_KERNEL=qsplit pins it)
-    int ginx_choice(const GateArgs& g) const;
+    // flags_.ginx_pin, the GINX kernel choice: 0 by batch size, 1 one wave per gate (K1), 2 two waves per gate
+    // with the digit exchange (K1s), 3 two waves per gate with K1w's one-word exchange (K1x), 4 K1q (four waves
+    // per gate, up to one gate per CU).  K1s is slower than K1 at every batch size (1024 gates 4.87 vs 4.37 ms:
+    // two barriers per index, the partner's digits read in the MAC) and only FHE_HIP_GINX_KERNEL=split pins it.
     // K1x runs batches of up to x_batch_ gates: one two-gate workgroup per CU (2 x the CU count, 512 on
     // MI355X).  Measured (tools/gate_time.py, STD128 AND, profiles/r06_k1x_ab2.txt): 512 gates 2.69 vs 4.16 ms
     // (K1), 768 gates 4.28 vs 4.18, 1024 gates 4.56 vs 4.24: once two of its waves share a SIMD they overlap
     // poorly, and the one-wave kernel wins.  Up to x_batch_ / 2 gates each gate has its own 128-thread workgroup
     // (a CU of its own: 1 gate 2.30 vs 2.64 ms, profiles/r06_k1x_lb_ab.txt); the LMKCDEY two-wave kernel likewise
     uint32_t x_batch_ = 512;
-    // LMKCDEY kernel choice on the fast path: 0 by batch size, 1 the one-wave op-list kernel (K1 LMK), 2 two
-    // waves per gate (K1m's two-digit form, k_blind_rotate_lmk3<2, ..>), 4 four waves per gate (K1m-4,
-    // k_blind_rotate_lmk4x) -- FHE_HIP_LMK_KERNEL = wave | split | qsplit
-    int lmk_kernel_ = 0;
-    // the kernel of this LMKCDEY launch: 1, 2 (up to x_batch_ gates) or 4 (up to x_batch_ / 2); lmk_kernel_ pins
-    int lmk_choice(const GateArgs& g) const;
-    void* d_bsk2_ = nullptr;   // K1s / K1x / K1m-2 key layout (g3_: K1s's nd = 3 layout; n2k_: K1w's)
+    // flags_.lmk_pin, the LMKCDEY kernel choice on the fast path: 0 by batch size, 1 the one-wave op-list kernel
+    // (K1 LMK), 2 two waves per gate (K1m's two-digit form, k_blind_rotate_lmk3<2, ..>, up to x_batch_ gates),
+    // 4 four waves per gate (K1m-4, k_blind_rotate_lmk4x, up to x_batch_ / 2)
+    DevArr<void> d_bsk2_;   // K1s / K1x / K1m-2 key layout (flags_.g3: K1s's nd = 3 layout; flags_.n2k: K1w's)
     void repack_ginx2();
-    // digitsG = 4 GINX sets at N = 1024, Q < 2^27 (STD128_3, STD128Q, STD128_4, LPF_STD128, LPF_STD128Q):
-    // gates on the split kernel with three digits per component (launch_blind_rotate_ginx3) over the
-    // 32-bit tables tabs_, the rest of the 64-bit path unchanged.  FHE_HIP_GINX3=0 keeps them on the 64-bit accumulator (A/B, tests).
-    bool g3_ = false;
+    // flags_.g3: digitsG = 4 GINX sets at N = 1024, Q < 2^27 (STD128_3, STD128Q, STD128_4, LPF_STD128,
+    // LPF_STD128Q): gates on the split kernel with three digits per component (launch_blind_rotate_ginx3) over the
+    // 32-bit tables tabs_, the rest of the 64-bit path unchanged.  FHE_HIP_GINX3=0 keeps them on the 64-bit
+    // accumulator (A/B, tests).
     void pack_ginx3(const uint64_t* bsk);
-    // GINX at N = 2048, Q < 2^27, digitsG = 4, q < 2N (STD256Q): gates on K1w (launch_blind_rotate_n2k)
-    // over its own 32-bit tables, keys packed into d_bsk2_; the rest of the 64-bit path (prep, key
-    // switch, functional bootstrapping) unchanged.  FHE_HIP_N2K=0 keeps them on K5 (A/B, tests).
-    bool n2k_ = false;
-    // the 32-bit key switch on the 64-bit path (ks32_set; g3_ sets always, FHE_HIP_KS32=0 keeps the
-    // u64 row gathers of launch_keyswitch_wide for the others: A/B, tests)
-    bool ks32_ = false;
-    bool ks32w_ = false;
-    uint32_t* d_ksk32_ = nullptr;  // ks32w_: u32 rows of ksk_width(n)
+    // flags_.n2k: GINX at N = 2048, Q < 2^27, digitsG = 4, q < 2N (STD256Q): gates on K1w
+    // (launch_blind_rotate_n2k) over its own 32-bit tables, keys packed into d_bsk2_; the rest of the 64-bit path
+    // (prep, key switch, functional bootstrapping) unchanged.  FHE_HIP_N2K=0 keeps them on K5 (A/B, tests).
+    // flags_.ks32 / ks32w: the 32-bit key switch on the 64-bit path (ks32_set; g3 sets always, FHE_HIP_KS32=0
+    // keeps the u64 row gathers of launch_keyswitch_wide for the others: A/B, tests)
+    DevArr<uint32_t> d_ksk32_;  // flags_.ks32w: u32 rows of ksk_width(n)
     BootTables tabs2k_{};
-    void* d_tables2k_ = nullptr;
+    DevArr<void> d_tables2k_;
     void build_tables_n2k();
     void pack_n2k(const uint64_t* bsk);
     // cross-stream ordering (use_stream)
     hipStream_t last_stream_ = nullptr;
     hipEvent_t order_ev_ = nullptr;
     bool pending_ = false;
-    // workspace; rot_count_ = ciphertexts the last blind rotation left in it
+    // workspace of cap_ ciphertexts (ensure_work grows the group together); rot_count_ = ciphertexts the last
+    // blind rotation left in it
     size_t cap_ = 0;
     size_t rot_count_ = 0;
-    uint16_t* d_idx_ = nullptr;
-    uint32_t* d_tvb_ = nullptr;
-    uint32_t* d_ext_a_ = nullptr;
-    uint32_t* d_ext_b_ = nullptr;
-    // CMUX: first-level NAND outputs [2 count][n] + [2 count] (ccap_: bytes)
-    size_t ccap_ = 0;
-    uint64_t* d_l1_ = nullptr;
-    // circuits: the ciphertext pool [rows][n] ++ [rows] and the descriptors (CircuitSlot[] ++ CircuitOut[]) of the
-    // circuit being evaluated; host staging of eval_circuit_host
-    size_t poolcap_ = 0, cdesccap_ = 0, ciocap_ = 0;
-    uint64_t cdesc_serial_ = 0;   // Circuit::serial() of the descriptors resident in d_cdesc_
-    uint64_t* d_pool_ = nullptr;
-    uint64_t* d_cdesc_ = nullptr;
-    uint64_t* d_cio_ = nullptr;
+    DevArr<uint16_t> d_idx_;
+    DevArr<uint32_t> d_tvb_;
+    DevArr<uint32_t> d_ext_a_;
+    DevArr<uint32_t> d_ext_b_;
+    DevArr<uint64_t> d_wext_a_;   // the 64-bit path's u64 ctExt
+    DevArr<uint64_t> d_wext_b_;
+    // grow-only scratch (reserve)
+    DevBuf l1_;      // CMUX: first-level NAND outputs [2 count][n] + [2 count]
+    DevBuf pool_;    // circuits: the ciphertext pool [rows][n] ++ [rows]
+    DevBuf cdesc_;   // ... and the descriptors (CircuitSlot[] ++ CircuitOut[] ++ ..) of the circuit being evaluated
+    uint64_t cdesc_serial_ = 0;   // Circuit::serial() of the descriptors resident in cdesc_
+    DevBuf mix_;     // mixed-modulus inputs: switched columns (eval_mixed_device)
+    DevBuf pkw_;     // public-key encryption: the packed ternary draws and SMALL_DIM's dimension-N ciphertexts
+    DevBuf tvbuf_;   // BootstrapFunc tables: u32 words (u64 on the wide path), grown with their count
+    DevBuf fb_;      // functional bootstrapping's ciphertext temporaries (fb_work)
+    DevBuf stage_;   // the synchronous host-buffer calls' staging (host_call; the C-ABI's seam calls)
     // prep of slots [first, first + g.count) of a circuit level into workspace slots [0, g.count)
     void prep_level_device(const GateArgs& g, const CircuitLevel& lv, hipStream_t s);
-    // mixed-modulus inputs: switched columns (eval_mixed_device) and the host entry point's staging
-    size_t mixcap_ = 0, mixiocap_ = 0;
-    uint64_t* d_mix_ = nullptr;
-    uint64_t* d_mixio_ = nullptr;
-    // public-key encryption: the resident key (pke.h pk_key_bytes), the packed ternary draws and SMALL_DIM's
-    // dimension-N ciphertexts (pkcap_: bytes), the host entry point's staging (pkiocap_)
-    void* d_pk_ = nullptr;
-    size_t pkcap_ = 0, pkiocap_ = 0;
-    uint64_t* d_pkw_ = nullptr;
-    uint64_t* d_pkio_ = nullptr;
-    // functional bootstrapping: test-vector table [2N] u32 and ciphertext temporaries
-    uint64_t* d_tvbuf_ = nullptr;   // BootstrapFunc tables: u32 words (u64 on the wide path), grown with their count
-    size_t tvcap_ = 0;
-    size_t fbcap_ = 0;
-    uint64_t* d_fb_ = nullptr;
-    // ExternalProduct: packed per-item keys and one-op lists (grown on demand)
+    DevArr<void> d_pk_;   // the resident public key (pke.h pk_key_bytes)
+    // ExternalProduct: packed per-item keys and one-op lists for epcap_ items (grown on demand)
     size_t epcap_ = 0;
-    uint32_t* d_epk_ = nullptr;
-    uint16_t* d_epops_ = nullptr;
-    uint32_t* d_epn_ = nullptr;
-    // staging for host entry points: up to 4 inputs + one ctExt-sized output
-    size_t hcap_ = 0;
-    uint64_t* d_io_ = nullptr;
-    // large-precision family: u64 keys (Montgomery BSK, raw KSK A ++ B), tables, u64 ctExt
-    bool wide_ = false;
-    // the wide accumulator in 32-bit residues (bootstrap_wide.hip A32): Q < 2^30 and digitsG2 Q < 2^32;
-    // d_bsk_ then holds u32 Montgomery words
-    bool narrow_ = false;
+    DevArr<uint32_t> d_epk_;
+    DevArr<uint16_t> d_epops_;
+    DevArr<uint32_t> d_epn_;
+    // the 64-bit path (flags_.wide: the large-precision family and every set outside fast_path): u64 keys
+    // (Montgomery BSK, raw KSK A ++ B), tables, u64 ctExt.  flags_.narrow: its accumulator in 32-bit residues
+    // (bootstrap_wide.hip A32: Q < 2^30 and digitsG2 Q < 2^32); d_bsk_ then holds u32 Montgomery words
     WideTables wtabs_{};
-    // word w of the resident wide keys (u64, or u32 when narrow_)
+    // word w of the resident wide keys (u64, or u32 when narrow)
     const void* wkey(size_t w) const {
-        return narrow_ ? (const void*)(static_cast<const uint32_t*>(d_bsk_) + w)
-                       : (const void*)(static_cast<const uint64_t*>(d_bsk_) + w);
+        return flags_.narrow ? (const void*)(d_bsk_.as<const uint32_t>() + w) : (const void*)(d_bsk_.as<const uint64_t>() + w);
     }
-    void* d_wtables_ = nullptr;
-    uint64_t* d_wksk_ = nullptr;
-    uint64_t* d_wext_a_ = nullptr;
-    uint64_t* d_wext_b_ = nullptr;
+    DevArr<void> d_wtables_;
+    DevArr<uint64_t> d_wksk_;
     // the key the wide kernel bootstraps with: the context's own baseG, or (timeOptimization) the
     // one EvalSign / EvalDecomp switched to (set_base); word offset into d_bsk_ and its digits
     Params cur_;

@@ -22,20 +22,6 @@ bool pow2(uint64_t x) { return x && !(x & (x - 1)); }
 // plan builds the same tables
 }  // namespace
 
-uint64_t* Engine::fb_work(size_t count, int cts) {
-    const size_t need = count * (size_t)cts;
-    if (need > fbcap_) {
-        FHE_HIP_CHECK(hipSetDevice(device_));
-        FHE_HIP_CHECK(hipDeviceSynchronize());
-        if (d_fb_) FHE_HIP_CHECK(hipFree(d_fb_));
-        d_fb_ = nullptr;
-        fbcap_ = 0;
-        FHE_HIP_CHECK(hipMalloc(&d_fb_, need * ((size_t)p_.n + 1) * 8));
-        fbcap_ = need;
-    }
-    return d_fb_;
-}
-
 void Engine::bootstrap_func_device(size_t count, const uint64_t* a, const uint64_t* b, uint32_t ctmod,
                                    const uint64_t* f, uint64_t fmod, uint64_t* a_out, uint64_t* b_out, hipStream_t s) {
     bootstrap_func_tables(count, a, b, ctmod, f, 1, fmod, a_out, b_out, s);
@@ -62,11 +48,12 @@ void Engine::bootstrap_func_tables(size_t count, const uint64_t* a, const uint64
         if (f[x] > fmod) throw std::invalid_argument("BootstrapFunc: f(x) exceeds fmod");
         tv[x] = scale * f[x];  // <= Q
     }
-    // the table region grows with the number of tables (grow: after the streams' earlier work that reads it)
+    // the table region grows with the number of tables (reserve: after the earlier work that reads it, this
+    // call's included)
     const size_t need = std::max<size_t>(words, 2 * (size_t)p_.N);
     // stream-ordered: the copy runs after every earlier launch on s that reads the table
-    uint64_t* t = grow(d_tvbuf_, tvcap_, need * (wide_ ? 8 : 4));
-    if (wide_) {
+    uint64_t* t = reserve(tvbuf_, need * (flags_.wide ? 8 : 4));
+    if (flags_.wide) {
         FHE_HIP_CHECK(hipMemcpyAsync(t, tv.data(), words * 8, hipMemcpyHostToDevice, s));
     } else {
         std::vector<uint32_t> tv32(tv.begin(), tv.end());
@@ -80,8 +67,8 @@ void Engine::bootstrap_func_tables(size_t count, const uint64_t* a, const uint64
     g.qKS = p_.qKS;
     g.ctmod = ctmod;
     g.factor = 2 * p_.N / ctmod;
-    g.tv = wide_ ? nullptr : reinterpret_cast<const uint32_t*>(t);
-    g.tv64 = wide_ ? t : nullptr;
+    g.tv = flags_.wide ? nullptr : reinterpret_cast<const uint32_t*>(t);
+    g.tv64 = flags_.wide ? t : nullptr;
     g.tv_mod = nt;
     g.b_const = 0;  // ctExt = (acc0, acc1[0]) (:624-626)
     g.msb_out = 1;
@@ -323,39 +310,6 @@ void Engine::eval_decomp_device(size_t count, const uint64_t* a, const uint64_t*
     }
     FHE_HIP_CHECK(hipMemcpyAsync(a_out + part * count * n, ta, count * n * 8, hipMemcpyDeviceToDevice, s));
     FHE_HIP_CHECK(hipMemcpyAsync(b_out + part * count, tb, count * 8, hipMemcpyDeviceToDevice, s));
-}
-
-void Engine::fb_host(int op, size_t count, const uint64_t* a, const uint64_t* b, uint64_t arg, uint64_t arg2,
-                     uint32_t iarg, const uint64_t* lut, uint64_t* a_out, uint64_t* b_out) {
-    if (!ready()) throw std::logic_error("keys not loaded (load_bsk / load_ksk)");
-    if (count == 0) return;
-    const size_t n = p_.n;
-    const size_t parts = op == 3 ? eval_decomp_parts(arg) : op == 5 ? iarg : 1;
-    FHE_HIP_CHECK(hipSetDevice(device_));
-    uint64_t* d = nullptr;
-    FHE_HIP_CHECK(hipMalloc(&d, count * (n + 1) * (1 + parts) * 8));
-    try {
-        uint64_t *da = d, *db = d + count * n, *oa = db + count, *ob = oa + parts * count * n;
-        FHE_HIP_CHECK(hipMemcpyAsync(da, a, count * n * 8, hipMemcpyHostToDevice, stream_));
-        FHE_HIP_CHECK(hipMemcpyAsync(db, b, count * 8, hipMemcpyHostToDevice, stream_));
-        switch (op) {
-            case 0: eval_func_device(count, da, db, arg, lut, oa, ob, stream_); break;
-            case 1: eval_floor_device(count, da, db, arg, iarg, oa, ob, stream_); break;
-            case 2: eval_sign_device(count, da, db, arg, iarg != 0, oa, ob, stream_); break;
-            case 3: eval_decomp_device(count, da, db, arg, oa, ob, stream_); break;
-            case 4: bootstrap_func_device(count, da, db, (uint32_t)arg, lut, arg2, oa, ob, stream_); break;
-            case 5: eval_func_multi_device(count, da, db, arg, lut, iarg, oa, ob, stream_); break;
-            default: throw std::invalid_argument("unknown functional-bootstrapping op");
-        }
-        FHE_HIP_CHECK(hipMemcpyAsync(a_out, oa, parts * count * n * 8, hipMemcpyDeviceToHost, stream_));
-        FHE_HIP_CHECK(hipMemcpyAsync(b_out, ob, parts * count * 8, hipMemcpyDeviceToHost, stream_));
-        FHE_HIP_CHECK(hipStreamSynchronize(stream_));
-    } catch (...) {
-        (void)hipStreamSynchronize(stream_);
-        (void)hipFree(d);
-        throw;
-    }
-    FHE_HIP_CHECK(hipFree(d));
 }
 
 }  // namespace fhe_amd

@@ -26,6 +26,13 @@ inline uint32_t reverse_bits(uint32_t x, uint32_t bits) {
 inline uint32_t ilog2(uint64_t x) { uint32_t r = 0; while (x > 1) { x >>= 1; ++r; } return r; }
 inline uint32_t shoup32(uint64_t w, uint64_t Q) { return (uint32_t)(((u128)w << 32) / Q); }
 inline uint64_t shoup64(uint64_t w, uint64_t Q) { return (uint64_t)(((u128)w << 64) / Q); }
+// the 32-bit kernels' Montgomery form x 2^32 mod Q and -Q^-1 mod 2^32 (Newton; Q odd: Q * Q = 1 mod 8)
+inline uint32_t to_mont(uint64_t x, uint64_t Q) { return (uint32_t)(((u128)(x % Q) << 32) % Q); }
+inline uint32_t neg_inv32(uint32_t Q) {
+    uint32_t x = Q;
+    for (int i = 0; i < 5; ++i) x *= 2 - Q * x;
+    return (uint32_t)(0u - x);
+}
 
 // Constants of the signed forward passes' first 4-point group (bootstrap.hip fwd_group4): with I = Table[1],
 // u = Table[2], v = Table[3] (plain residues mod an odd prime Q), the two stage-2 products of a group are

@@ -2,7 +2,7 @@
 ciphertext moduli q and 2N, EvalFunc with an arbitrary LUT, and gates, for the default context (K1x for GINX,
 K1m's two-digit form for LMKCDEY, up to two gates per CU) and with FHE_HIP_{GINX,LMK}_KERNEL=wave (K1).
 Host-buffer entry points, median of `reps` calls.
-usage: python tools/small_batch_time.py [reps] [paramset name] [GINX | LMKCDEY]"""
+usage: python tools/small_batch_time.py [reps] [paramset name] [GINX | LMKCDEY] [counts, default 1,64,512]"""
 import os
 import sys
 import time
@@ -15,6 +15,7 @@ from fhe_amd import binfhe as bf  # noqa: E402
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
 ps = bf.PARAMSETS.index(sys.argv[2]) if len(sys.argv) > 2 else bf.STD128
 m = bf.LMKCDEY if len(sys.argv) > 3 and sys.argv[3] == "LMKCDEY" else bf.GINX
+counts = tuple(int(c) for c in sys.argv[4].split(",")) if len(sys.argv) > 4 else (1, 64, 512)
 knob = "FHE_HIP_LMK_KERNEL" if m == bf.LMKCDEY else "FHE_HIP_GINX_KERNEL"
 keys = bf.keygen(ps, m, 3)
 P = bf.params(ps, m)
@@ -38,7 +39,7 @@ for kind in ("default", "wave"):
     os.environ.pop(knob, None)
     e.load_keys(keys.bsk, keys.kskA, keys.kskB)
     out = []
-    for cnt in (1, 64, 512):
+    for cnt in counts:
         a = rng.integers(0, P.q, (cnt, P.n), dtype=np.uint64)
         b = rng.integers(0, P.q, cnt, dtype=np.uint64)
         a2 = rng.integers(0, 2 * P.N, (cnt, P.n), dtype=np.uint64)
