@@ -36,6 +36,14 @@ def lib():
         L.fhe_hip_ntt_batch_device.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp]
         L.fhe_hip_ntt_plan_stream.argtypes = [vp]
         L.fhe_hip_ntt_plan_stream.restype = vp
+        L.fhe_hip_ntt_plan_n.argtypes = [vp]
+        L.fhe_hip_ntt_plan_n.restype = ctypes.c_uint32
+        L.fhe_hip_poly_mul_batch.argtypes = [vp, vp, vp, vp, sz]
+        L.fhe_hip_poly_mul_batch_device.argtypes = [vp, vp, vp, vp, sz, vp]
+        L.fhe_hip_ntt_onepass_max.argtypes = [ctypes.c_int]
+        L.fhe_hip_ntt_onepass_max.restype = ctypes.c_uint32
+        L.fhe_hip_ntt_plan_dispatch.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.fhe_hip_ntt_plan_set_onepass_max.argtypes = [vp, ctypes.c_uint32]
         L.fhe_hip_alloc.argtypes = [ctypes.c_int, sz, ctypes.POINTER(vp)]
         L.fhe_hip_free.argtypes = [vp]
         L.fhe_hip_copy_to_device.argtypes = [vp, vp, sz]

@@ -107,9 +107,24 @@ struct fhe_hip_multi {
 struct fhe_hip_ntt_plan {
     NttPlan plan;
     hipStream_t stream = nullptr;
-    uint64_t* d_buf    = nullptr;
+    uint64_t* d_buf    = nullptr;  // host-buffer calls: the batch (the product's two operands)
     size_t cap         = 0;
+    uint64_t* d_tmp    = nullptr;  // fhe_hip_poly_mul_batch_device: the transform of b
+    size_t tmp_cap     = 0;
 };
+
+// grows a plan-owned device buffer to at least `bytes`.  Earlier asynchronous work may still use the old
+// block: hipFree waits for the device before it releases it, so a growing call is safe but stalls the
+// device once; calls that fit the buffer allocate nothing
+static hipError_t plan_reserve(uint64_t** buf, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return hipSuccess;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc(buf, bytes);
+    if (e == hipSuccess) *cap = bytes;
+    return e;
+}
 
 extern "C" {
 
@@ -159,12 +174,13 @@ int fhe_hip_ntt_plan_create(uint64_t Q, uint64_t psi, uint32_t N, int device, fh
     return guarded([&]() -> int {
         if (!out) return fail(FHE_HIP_ERR_NULL_PTR, "out is null");
         *out   = nullptr;
+        if (const char* why = ntt_plan_check(Q, N))
+            return fail(FHE_HIP_ERR_INVALID_PARAM, std::string("invalid NTT parameters: ") + why);
         auto* p = new fhe_hip_ntt_plan();
         hipError_t e = ntt_plan_init(p->plan, Q, psi, N, device);
         if (e == hipErrorInvalidValue) {
             delete p;
-            return fail(FHE_HIP_ERR_INVALID_PARAM, "invalid NTT parameters (need N=1024, prime Q=1 mod 2N, Q<2^62, "
-                                                   "psi a primitive 2N-th root)");
+            return fail(FHE_HIP_ERR_INVALID_PARAM, "invalid NTT parameters: psi must be a primitive 2N-th root of unity");
         }
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
@@ -182,6 +198,7 @@ void fhe_hip_ntt_plan_destroy(fhe_hip_ntt_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->plan.device);
     if (p->d_buf) (void)hipFree(p->d_buf);
+    if (p->d_tmp) (void)hipFree(p->d_tmp);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     ntt_plan_free(p->plan);
     delete p;
@@ -189,15 +206,75 @@ void fhe_hip_ntt_plan_destroy(fhe_hip_ntt_plan* p) {
 
 void* fhe_hip_ntt_plan_stream(fhe_hip_ntt_plan* p) { return p ? (void*)p->stream : nullptr; }
 
+uint32_t fhe_hip_ntt_plan_n(fhe_hip_ntt_plan* p) { return p ? p->plan.N : 0; }
+
+uint32_t fhe_hip_ntt_onepass_max(int wide) { return ntt_onepass_default(wide != 0); }
+
+int fhe_hip_ntt_plan_dispatch(fhe_hip_ntt_plan* p, uint32_t* passes, uint32_t* polys_per_group) {
+    if (!p || !passes || !polys_per_group) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    ntt_dispatch_info(p->plan, passes, polys_per_group);
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_ntt_plan_set_onepass_max(fhe_hip_ntt_plan* p, uint32_t n) {
+    if (!p) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (!ntt_onepass_valid(n))
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "one-pass limit must be a power of two in 2048 .. 16384");
+    p->plan.log_onepass = ilog2(n);
+    return FHE_HIP_OK;
+}
+
 int fhe_hip_ntt_batch_device(fhe_hip_ntt_plan* p, const uint64_t* d_in, uint64_t* d_out, size_t count, int inverse,
                              void* stream) {
     if (!p || (!d_in && count) || (!d_out && count)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
     if (count > 0xffffffffull) return fail(FHE_HIP_ERR_INVALID_PARAM, "count too large");
     hipError_t e = hipSetDevice(p->plan.device);
     if (e == hipSuccess)
-        e = ntt1024_launch(p->plan, d_in, d_out, (uint32_t)count, inverse != 0,
-                           stream ? (hipStream_t)stream : p->stream);
+        e = ntt_launch(p->plan, d_in, d_out, (uint32_t)count, inverse != 0, stream ? (hipStream_t)stream : p->stream);
     return e == hipSuccess ? FHE_HIP_OK : hip_fail(e, "ntt launch");
+}
+
+// out = iNTT(NTT(a) . NTT(b)) with buf = [a | b] (2 x count polynomials): one forward launch over
+// both operands, the pointwise product into a's half, one inverse launch
+static hipError_t poly_mul_inplace(const NttPlan& plan, uint64_t* buf, uint32_t count, hipStream_t s) {
+    const size_t words = (size_t)count * plan.N;
+    hipError_t e       = ntt_launch(plan, buf, buf, 2 * count, false, s);
+    if (e == hipSuccess) e = ntt_pointwise_mul(plan, buf, buf + words, buf, words, s);
+    if (e == hipSuccess) e = ntt_launch(plan, buf, buf, count, true, s);
+    return e;
+}
+
+int fhe_hip_poly_mul_batch(fhe_hip_ntt_plan* p, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count) {
+    if (!p || ((!a || !b || !out) && count)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (count > 0x7fffffffull) return fail(FHE_HIP_ERR_INVALID_PARAM, "count too large");
+    if (count == 0) return FHE_HIP_OK;
+    hipError_t e       = hipSetDevice(p->plan.device);
+    const size_t bytes = count * p->plan.N * sizeof(uint64_t);
+    if (e == hipSuccess) e = plan_reserve(&p->d_buf, &p->cap, 2 * bytes);
+    uint64_t* d_b = p->d_buf + count * p->plan.N;
+    if (e == hipSuccess) e = hipMemcpyAsync(p->d_buf, a, bytes, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_b, b, bytes, hipMemcpyHostToDevice, p->stream);
+    if (e == hipSuccess) e = poly_mul_inplace(p->plan, p->d_buf, (uint32_t)count, p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, p->d_buf, bytes, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    return e == hipSuccess ? FHE_HIP_OK : hip_fail(e, "poly mul batch");
+}
+
+int fhe_hip_poly_mul_batch_device(fhe_hip_ntt_plan* p, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out,
+                                  size_t count, void* stream) {
+    if (!p || ((!d_a || !d_b || !d_out) && count)) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (count > 0xffffffffull) return fail(FHE_HIP_ERR_INVALID_PARAM, "count too large");
+    if (count == 0) return FHE_HIP_OK;
+    hipStream_t s      = stream ? (hipStream_t)stream : p->stream;
+    hipError_t e       = hipSetDevice(p->plan.device);
+    const size_t words = count * p->plan.N;
+    if (e == hipSuccess) e = plan_reserve(&p->d_tmp, &p->tmp_cap, words * sizeof(uint64_t));
+    // b first: d_out may be d_a or d_b
+    if (e == hipSuccess) e = ntt_launch(p->plan, d_b, p->d_tmp, (uint32_t)count, false, s);
+    if (e == hipSuccess) e = ntt_launch(p->plan, d_a, d_out, (uint32_t)count, false, s);
+    if (e == hipSuccess) e = ntt_pointwise_mul(p->plan, d_out, p->d_tmp, d_out, words, s);
+    if (e == hipSuccess) e = ntt_launch(p->plan, d_out, d_out, (uint32_t)count, true, s);
+    return e == hipSuccess ? FHE_HIP_OK : hip_fail(e, "poly mul launch");
 }
 
 int fhe_hip_ntt_batch(fhe_hip_ntt_plan* p, uint64_t* polys, size_t count, int inverse) {
@@ -205,15 +282,9 @@ int fhe_hip_ntt_batch(fhe_hip_ntt_plan* p, uint64_t* polys, size_t count, int in
     if (count == 0) return FHE_HIP_OK;
     hipError_t e = hipSetDevice(p->plan.device);
     const size_t bytes = count * p->plan.N * sizeof(uint64_t);
-    if (e == hipSuccess && bytes > p->cap) {
-        if (p->d_buf) (void)hipFree(p->d_buf);
-        p->d_buf = nullptr;
-        p->cap   = 0;
-        e        = hipMalloc(&p->d_buf, bytes);
-        if (e == hipSuccess) p->cap = bytes;
-    }
+    if (e == hipSuccess) e = plan_reserve(&p->d_buf, &p->cap, bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(p->d_buf, polys, bytes, hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) e = ntt1024_launch(p->plan, p->d_buf, p->d_buf, (uint32_t)count, inverse != 0, p->stream);
+    if (e == hipSuccess) e = ntt_launch(p->plan, p->d_buf, p->d_buf, (uint32_t)count, inverse != 0, p->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(polys, p->d_buf, bytes, hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     return e == hipSuccess ? FHE_HIP_OK : hip_fail(e, "ntt batch");

@@ -1,4 +1,4 @@
-// ntt_plan.cpp -- builds and uploads the twiddle tables for ntt.hip.
+// ntt_plan.cpp -- builds and uploads the twiddle tables for ntt.hip and ntt_sizes.hip.
 #include <vector>
 
 #include "nt.h"
@@ -6,21 +6,34 @@
 
 namespace fhe_amd {
 
+const char* ntt_plan_check(uint64_t Q, uint32_t N) {
+    if (N < 4 || N > 65536 || (N & (N - 1)) != 0) return "N must be a power of two in 4 .. 65536";
+    if (Q < 3 || Q >= (1ull << 62)) return "Q must be below 2^62";
+    if ((Q - 1) % (2 * (uint64_t)N) != 0) return "Q must be 1 mod 2N";
+    if (!is_prime(Q)) return "Q must be prime";
+    return nullptr;
+}
+
 hipError_t ntt_plan_init(NttPlan& p, uint64_t Q, uint64_t psi, uint32_t N, int device) {
-    if (N != 1024) return hipErrorInvalidValue;
-    if (Q < 3 || Q >= (1ull << 62) || (Q - 1) % (2 * N) != 0 || !is_prime(Q)) return hipErrorInvalidValue;
+    if (ntt_plan_check(Q, N)) return hipErrorInvalidValue;
     if (psi == 0) psi = root_of_unity(2 * N, Q);
     if (powmod(psi, N, Q) != Q - 1) return hipErrorInvalidValue;  // must be a primitive 2N-th root
     HostNtt h;
     h.init(N, Q, psi);
     p.Q = Q; p.psi = psi; p.N = N; p.device = device;
     p.wide = Q >= (1ull << 30);  // the 32-bit path keeps lazy values below 4Q < 2^32
+    p.log_onepass = ilog2(ntt_onepass_default(p.wide));
+    p.qinv64 = Q;  // Q^-1 mod 2^64 by Newton iteration (Q Q = 1 mod 8)
+    for (int k = 0; k < 6; ++k) p.qinv64 *= 2 - Q * p.qinv64;
+    const uint64_t r1 = (uint64_t)(((u128)1 << 64) % Q);
+    p.r2 = mulmod(r1, r1, Q);
     const uint64_t w1 = h.tabI[1];
     p.ninv = h.ninv;
     p.w1ninv = mulmod(w1, h.ninv, Q);
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return e;
     if ((e = hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return e;
+    if (N != 1024 && (e = ntt_sizes_prepare()) != hipSuccess) return e;
     if (!p.wide) {
         std::vector<uint32_t> f(2 * N), iv(2 * N);
         for (uint32_t i = 0; i < N; ++i) {
@@ -33,7 +46,7 @@ hipError_t ntt_plan_init(NttPlan& p, uint64_t Q, uint64_t psi, uint32_t N, int d
         if ((e = hipMalloc(&p.d_tab_inv, iv.size() * 4)) != hipSuccess) return e;
         if ((e = hipMemcpy(p.d_tab_fwd, f.data(), f.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
         if ((e = hipMemcpy(p.d_tab_inv, iv.data(), iv.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if (Q < (1ull << 27)) {
+        if (N == 1024 && Q < (1ull << 27)) {  // k_ntt1024w's signed kernel
             auto mont = [&](uint64_t x) { return (uint32_t)(((x % Q) << 32) % Q); };
             std::vector<uint32_t> fm(N), im(N);
             for (uint32_t i = 0; i < N; ++i) {
@@ -59,7 +72,7 @@ hipError_t ntt_plan_init(NttPlan& p, uint64_t Q, uint64_t psi, uint32_t N, int d
         }
         p.ninv_pre = shoup64(p.ninv, Q);
         p.w1ninv_pre = shoup64(p.w1ninv, Q);
-        for (uint32_t S = 1; S < 20; ++S)
+        for (uint32_t S = 1; N == 1024 && S < 20; ++S)  // k_ntt1024w64's Sol60 butterflies
             if (Q == (1ull << 60) - ((1ull << S) - 1)) p.sol_shift = S;
         if ((e = hipMalloc(&p.d_tab_fwd, f.size() * 8)) != hipSuccess) return e;
         if ((e = hipMalloc(&p.d_tab_inv, iv.size() * 8)) != hipSuccess) return e;

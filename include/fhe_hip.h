@@ -49,9 +49,12 @@ enum {
 /* ------------------------------------------------------------------------ */
 typedef struct fhe_hip_ntt_plan fhe_hip_ntt_plan;
 
-/* N must be 1024; Q prime, Q = 1 mod 2N, Q < 2^62.  psi = 0 picks the
+/* N a power of two, 4 <= N <= 65536; Q prime, Q = 1 mod 2N, Q < 2^62; anything else
+ * is FHE_HIP_ERR_INVALID_PARAM, and fhe_hip_last_error() says which.  psi = 0 picks the
  * reference's root (minimal primitive 2N-th root, nbtheory-impl.h:183-228);
- * *psi_out (optional) receives the root used. */
+ * *psi_out (optional) receives the root used.  N = 1024 runs the one-polynomial-per-wave
+ * kernels; every other N the LDS stage kernels: one pass up to fhe_hip_ntt_onepass_max(),
+ * two passes above. */
 int fhe_hip_ntt_plan_create(uint64_t Q, uint64_t psi, uint32_t N, int device, fhe_hip_ntt_plan** out,
                             uint64_t* psi_out);
 void fhe_hip_ntt_plan_destroy(fhe_hip_ntt_plan* plan);
@@ -64,6 +67,29 @@ int fhe_hip_ntt_batch_device(fhe_hip_ntt_plan* plan, const uint64_t* d_in, uint6
                              int inverse, void* stream);
 /* the plan's stream (hipStream_t) */
 void* fhe_hip_ntt_plan_stream(fhe_hip_ntt_plan* plan);
+/* the plan's ring dimension (0 for a NULL plan) */
+uint32_t fhe_hip_ntt_plan_n(fhe_hip_ntt_plan* plan);
+/* Negacyclic product out = a b mod (X^N + 1, Q) of count polynomial pairs: two forward
+ * transforms, a pointwise product, one inverse (the reference's SwitchFormat / Times /
+ * SwitchFormat).  a, b and out are in COEFFICIENT form, canonical words; out may be a or b.
+ * The host call is synchronous (count < 2^31).  The device call is asynchronous on `stream`
+ * (NULL = plan stream) and keeps the transform of b in a buffer the plan owns: calls on one
+ * plan go to one stream, or the caller orders them. */
+int fhe_hip_poly_mul_batch(fhe_hip_ntt_plan* plan, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t count);
+int fhe_hip_poly_mul_batch_device(fhe_hip_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out,
+                                  size_t count, void* stream);
+/* How a plan is dispatched.  fhe_hip_ntt_onepass_max: the largest N (N != 1024) transformed in one
+ * pass with the polynomial in LDS, per arithmetic width (wide = Q >= 2^30); larger N take two passes.
+ * fhe_hip_ntt_plan_dispatch: the plan's passes (1 or 2) and the polynomials one workgroup
+ * transforms.
+ * Measurement hook, not part of the stable interface: fhe_hip_ntt_plan_set_onepass_max moves one
+ * plan's cut (a power of two in 2048 .. 16384; results do not change) so that tools/ntt_sizes_time.py
+ * can run both sides of it.  The cut is read on the host when a call enqueues its launches, so work
+ * already enqueued is unaffected and only later calls change; like every call on a plan it is not
+ * thread-safe. */
+uint32_t fhe_hip_ntt_onepass_max(int wide);
+int fhe_hip_ntt_plan_dispatch(fhe_hip_ntt_plan* plan, uint32_t* passes, uint32_t* polys_per_group);
+int fhe_hip_ntt_plan_set_onepass_max(fhe_hip_ntt_plan* plan, uint32_t n);
 
 /* ------------------------------------------------------------------------ */
 /* Gate bootstrapping context (one per device).                             */
