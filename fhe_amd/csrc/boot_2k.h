@@ -11,8 +11,8 @@
 //   fwd_2k_s<NP, QM>   signed forward transform A -> C of NP polynomials through the one tile; QM is the modulus
 //                      class that places its reductions (none for Q < 2^27; see red_2k and FHE_FWD_TIGHT)
 //   inv_2k_s<BIN, LIM> signed inverse C -> A from |v| < BIN Q / 10 to canonical [0, Q), with the compile-time
-//                      reduction plan InvPlan2k for LIM / 10 Q of signed headroom; the keys carry N^-1, so the
-//                      last stage scales by TableI[1] (w1R) only
+//                      reduction plan of red_plan.h (N2kShape, thresholds searched) for LIM / 10 Q of signed
+//                      headroom; the keys carry N^-1, so the last stage scales by TableI[1] (w1R) only
 #pragma once
 #include "boot_arith.h"
 
@@ -132,69 +132,6 @@ FHE_DEV void fwd_2k_s(uint32_t (&v)[NP][32], uint32_t* t, int L, const uint32_t*
     }
 }
 
-// the signed inverse's reduction plan (as InvPlanS / make_inv_plan_ww): stage st = 0 (C, register bit
-// 0), 1..5 (B, register bits 0..4), 6..9 (A, register bits 0..3), 10 (the last, register bit 4); a
-// transpose precedes stages 1 and 6
-struct InvPlan2k {
-    bool red[11][32];
-    bool redT[2][32];  // before the C -> B / B -> A transpose (as InvPlanWW)
-    int fin[16];
-    int cost;
-};
-template <int BIN, int LIM>
-constexpr InvPlan2k inv_plan_2k_t(int T0, int T1) {
-    InvPlan2k p{};
-    int B[32] = {};
-    for (int r = 0; r < 32; ++r) B[r] = BIN;
-    const int bits[11] = {0, 0, 1, 2, 3, 4, 0, 1, 2, 3, 4};
-    int nred = 0;
-    for (int st = 0; st < 11; ++st) {
-        if (st == 1 || st == 6) {
-            const int k = st == 1 ? 0 : 1, T = k ? T1 : T0;
-            int U = 0;
-            for (int r = 0; r < 32; ++r) {
-                if (B[r] > T) {
-                    B[r]         = 10;
-                    p.redT[k][r] = true;
-                    ++nred;
-                }
-                U = B[r] > U ? B[r] : U;
-            }
-            for (int r = 0; r < 32; ++r) B[r] = U;
-        }
-        const int bt = bits[st];
-        for (int r = 0; r < 32; ++r) {
-            if (r & (1 << bt)) continue;
-            const int q = r | (1 << bt);
-            while (B[r] + B[q] > LIM) {
-                const int e = B[r] >= B[q] ? r : q;
-                B[e]        = 10;
-                p.red[st][e] = true;
-                ++nred;
-            }
-            if (st == 10) {
-                int f = 0;
-                while ((10 << f) < B[r] + B[q]) ++f;
-                p.fin[r] = f;
-            }
-            B[r] = B[r] + B[q];
-            B[q] = 10;
-        }
-    }
-    p.cost = 2 * nred;
-    for (int r = 0; r < 16; ++r) p.cost += p.fin[r] + 1;
-    return p;
-}
-template <int BIN, int LIM>
-constexpr InvPlan2k make_inv_plan_2k() {
-    InvPlan2k best = inv_plan_2k_t<BIN, LIM>(kPlanT[7], kPlanT[7]);
-    for (int a = 0; a < kPlanTN; ++a)
-        for (int b = 0; b < kPlanTN; ++b) {
-            const InvPlan2k p = inv_plan_2k_t<BIN, LIM>(kPlanT[a], kPlanT[b]);
-            if (p.cost < best.cost) best = p;
-        }
-    return best;
-}
 // signed inverse NTT, layout C (EVAL, |v| < BIN Q / 10) -> A (COEF), canonical [0, Q); the keys carry
 // N^-1, so the last stage scales by TableI[1] only (w1R)
 // LIM: the signed headroom in units of Q/10 (160: Q < 2^27; 80: Q < 2^28, where the last stage's
@@ -202,31 +139,16 @@ constexpr InvPlan2k make_inv_plan_2k() {
 template <int BIN, int LIM = 160>
 FHE_DEV void inv_2k_s(uint32_t (&v)[32], uint32_t* t, int L, const uint32_t* __restrict__ twAi,
                       const uint32_t* s_tabI, uint32_t w1R, uint32_t oneR, const Mod& m) {
-    constexpr InvPlan2k P = make_inv_plan_2k<BIN, LIM>();
-    auto redp = [&](int st) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r)
-            if (P.red[st][r]) v[r] = smont_mul(v[r], oneR, m);
-    };
-    auto redt = [&](int k) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r)
-            if (P.redT[k][r]) v[r] = smont_mul(v[r], oneR, m);
-    };
-    auto gs = [&](uint32_t& x, uint32_t& y, uint32_t w) {
-        const uint32_t s = x + y;
-        y                = smont_mul(x - y, w, m);
-        x                = s;
-    };
+    constexpr RedPlan<N2kShape> P = red_plan_search<N2kShape>(BIN, LIM);
     const int G = L >> 1;
     uint32_t* ta = t + wa2k(L);
     uint32_t* tb = t + wb2k(L);
     uint32_t* tc = t + wc2k(L);
-    redp(0);
+    red_row(v, P.red[0], oneR, m);
 #pragma unroll
-    for (int rh = 0; rh < 16; ++rh) gs(v[2 * rh], v[2 * rh + 1], s_tabI[1024 + (rh << 6) + L]);
+    for (int rh = 0; rh < 16; ++rh) gs_bf_s(v[2 * rh], v[2 * rh + 1], s_tabI[1024 + (rh << 6) + L], m);
     // C -> B
-    redt(0);
+    red_row(v, P.redT[0], oneR, m);
 #pragma unroll
     for (int rh = 0; rh < 16; ++rh)
         *reinterpret_cast<uint2*>(tc + 132 * rh) = make_uint2(v[2 * rh], v[2 * rh + 1]);
@@ -237,15 +159,15 @@ FHE_DEV void inv_2k_s(uint32_t (&v)[32], uint32_t* t, int L, const uint32_t* __r
 #pragma unroll
     for (int b = 1; b <= 5; ++b) {
         const int rb = b - 1;
-        redp(b);
+        red_row(v, P.red[b], oneR, m);
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], s_tabI[(1 << (10 - b)) + (G << (5 - b)) + (r >> b)]);
+            gs_bf_s(v[r], v[r | (1 << rb)], s_tabI[(1 << (10 - b)) + (G << (5 - b)) + (r >> b)], m);
         }
     }
     // B -> A
-    redt(1);
+    red_row(v, P.redT[1], oneR, m);
 #pragma unroll
     for (int r = 0; r < 32; ++r) tb[2 * r] = v[r];
     wave_lds_sync();
@@ -255,25 +177,17 @@ FHE_DEV void inv_2k_s(uint32_t (&v)[32], uint32_t* t, int L, const uint32_t* __r
 #pragma unroll
     for (int b = 6; b <= 9; ++b) {
         const int rb = b - 6;
-        redp(b);
+        red_row(v, P.red[b], oneR, m);
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], twAi[(1 << (10 - b)) + (r >> (rb + 1))]);
+            gs_bf_s(v[r], v[r | (1 << rb)], twAi[(1 << (10 - b)) + (r >> (rb + 1))], m);
         }
     }
-    // bit 10 (transformnat-impl.h:599-623), canonical results as inv_pass_s
-    redp(10);
+    // bit 10, canonical results (gs_last_s)
+    red_row(v, P.red[10], oneR, m);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const uint32_t x = v[r], y = v[r | 16];
-        uint32_t s       = x + y + (m.Q << P.fin[r]);
-#pragma unroll
-        for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
-        const uint32_t d = smont_mul(x - y, w1R, m);
-        v[r]             = s;
-        v[r | 16]        = min(d, d + m.Q);
-    }
+    for (int r = 0; r < 16; ++r) gs_last_s(v[r], v[r | 16], P.fin[r], w1R, m);
 }
 
 }  // namespace

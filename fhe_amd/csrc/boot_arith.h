@@ -2,18 +2,21 @@
 // N = 2048 (boot_2k.h, boot_n2k_ginx.hip, boot_n2k_lmk.hip) share; include it from .hip files only.  boot.h stays
 // the host-visible interface (argument blocks, layouts, launchers).
 //
-// Residues are 32-bit words mod Q (Mod, from BootTables).  Signed residues (smont_mul, smont_red, ct_bf_s): the
-// word read as int32, a Montgomery product in (-Q, Q) (more exactly below |a| Q 2^-32 + Q/2), butterflies of two
+// Residues are 32-bit words mod Q (Mod, from BootTables).  Signed residues (smont_mul, smont_red, ct_bf_s, gs_bf_s):
+// the word read as int32, a Montgomery product in (-Q, Q) (more exactly below |a| Q 2^-32 + Q/2), butterflies of two
 // adds with no offset and no reduction; one product with oneR = 2^32 mod Q brings a value back to (-Q, Q).  32-bit
-// words leave 16 Q of headroom for Q < 2^27, 8 Q for Q < 2^28, 4 Q for Q < 2^29.  mont_mul is the unsigned lazy
-// product (result below 2 Q).  Also here: the digit decomposition for ND retained digits (DecN, decompose_n), the
-// wave-local LDS hand-off (wave_lds_sync), ModSwitch in integers (mod_switch), the thresholds the wave-wide inverse
-// plans search (kPlanT), and FHE_FWD_TIGHT, the one A/B knob both sides read.
+// words leave 16 Q of headroom for Q < 2^27, 8 Q for Q < 2^28, 4 Q for Q < 2^29.  The signed inverse transforms
+// place those products by a compile-time plan (red_plan.h, included here; lim_s is its LIM) and apply it with
+// red_row, gs_bf_s and gs_last_s.  mont_mul is the unsigned lazy product (result below 2 Q).  Also here: the digit
+// decomposition for ND retained digits (DecN, decompose_n), the wave-local LDS hand-off (wave_lds_sync), ModSwitch
+// in integers (mod_switch), and FHE_FWD_TIGHT, the one A/B knob both sides read.
 // The boundary is deliberate: only what both sides read is here.  What bootstrap.hip alone uses (mont_red, mac4,
-// ct_bf, gs_bf, fwd_group4, transpose32, Dec / dec_leg, other_half, kload, brv5, the other knobs) stays there.
+// ct_bf, gs_bf, fwd_group4, transpose32, Dec / dec_leg / dec_leg2, other_half, kload, brv5, the other knobs) stays
+// there.
 #pragma once
 #include "arith.h"
 #include "boot.h"
+#include "red_plan.h"
 
 // Forward-transform bounds from the product itself (round 5): a signed Montgomery product is below
 // |y| |w| 2^-32 + Q/2 < (Q / 2^32) |y| + Q/2, so a Cooley-Tukey stage takes a bound B to (1 + Q / 2^32) B + Q/2
@@ -77,6 +80,34 @@ FHE_DEV void ct_bf_s(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     y                = x - t;
     x                = x + t;
 }
+// signed Gentleman-Sande: x' = x + y, y' = (x - y) w in (-Q, Q); |x| + |y| must stay below 2^31, which the
+// reduction plan (red_plan.h) sees to
+FHE_DEV void gs_bf_s(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
+    const uint32_t t = x + y;
+    y                = smont_mul(x - y, wR, m);
+    x                = t;
+}
+// LIM of the plans: the bound on |x| + |y| (units of Q/10) that keeps sums below 2^31: 16 Q for Q < 2^27,
+// 8 Q for Q < 2^28
+constexpr int lim_s(bool lz) { return lz ? 160 : 80; }
+// the registers a plan row marks (RedPlan::red[s], redT[k]) back to (-Q, Q)
+template <int R>
+FHE_DEV void red_row(uint32_t (&v)[R], const bool (&row)[R], uint32_t oneR, const Mod& m) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (row[r]) v[r] = smont_mul(v[r], oneR, m);
+}
+// a pair of the last inverse stage (transformnat-impl.h:599-623; the N^-1 factor is already in the data) to
+// canonical [0, Q): the sum, |x + y| < 2^fin Q (RedPlan::fin), by adding 2^fin Q and fin + 1 conditional
+// subtractions, the product (in (-Q, Q)) by min(d, d + Q) on the unsigned words
+FHE_DEV void gs_last_s(uint32_t& x, uint32_t& y, int fin, uint32_t w1R, const Mod& m) {
+    uint32_t s = x + y + (m.Q << fin);
+#pragma unroll
+    for (int f = fin; f >= 0; --f) s = csub(s, m.Q << f);
+    const uint32_t d = smont_mul(x - y, w1R, m);
+    x                = s;
+    y                = min(d, d + m.Q);
+}
 
 // intra-wave LDS hand-off: orders this wave's LDS accesses around a layout change
 FHE_DEV void wave_lds_sync() {
@@ -117,15 +148,6 @@ FHE_DEV void decompose_n(uint32_t x, const DecN& c, uint32_t (&d)[ND][R], int r)
 #pragma unroll
     for (int j = 0; j < ND; ++j) d[j][r] = (uint32_t)__builtin_amdgcn_sbfe(w, (j + 1) * c.g, c.g);
 }
-
-// The wave-wide inverse plans (bootstrap.hip make_inv_plan_ww, boot_2k.h make_inv_plan_2k) reduce registers whose
-// bound exceeds a threshold before each of their two transposes, and search these thresholds for the cheapest plan
-// (units of Q/10)
-constexpr int kPlanT[8] = {10, 15, 20, 30, 40, 60, 80, 1 << 20};  // candidate thresholds (the last: none)
-#ifndef FHE_PLAN_T
-#define FHE_PLAN_T 1  // 0: no reductions before the transposes (the round-4 plans)
-#endif
-constexpr int kPlanTN = FHE_PLAN_T ? 8 : 0;
 
 }  // namespace
 

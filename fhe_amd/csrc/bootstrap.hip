@@ -53,7 +53,7 @@
 // half a Q more on the group's outputs.  For FM 2 that takes the 6.67 Q of FHE_FWD_TIGHT (boot_arith.h) to 7.43 Q
 // (still inside 8 Q) and
 // the LMKCDEY accumulator bound from 2.2 Q to 2.4 Q (four digits < 7.44 Q times keys < Q: 29.8 Q^2 2^-32 + Q/2
-// < 2.36 Q); make_inv_plan and make_inv_plan_ww give the same reductions for 2.4 Q as for 2.2 Q.
+// < 2.36 Q); the half-wave and wave reduction plans (red_plan.h) cost the same for 2.4 Q as for 2.2 Q.
 // FHE_FWD_GROUP=0: ten radix-2 stages (A/B).
 #ifndef FHE_FWD_GROUP
 #define FHE_FWD_GROUP 1
@@ -321,67 +321,9 @@ FHE_DEV void inv_pass(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* 
 }
 
 // ---- signed inverse NTT (Q < 2^27) ------------------------------------------------------------
-// Gentleman-Sande on signed residues: x' = x + y, y' = smont(x - y, w) in (-Q, Q): two adds and
-// no reduction per butterfly.  Sums grow; |x +- y| must stay < 2^31 = 16Q, so elements whose
-// bound would overflow are brought back to (-Q, Q) by one signed Montgomery product with 2^32 mod Q.
-// Bounds are tracked per register at compile time (units of Q/10): in layout B' the register index
-// is the slot's low 5 bits, so the bound of every element a register holds is the same.  At the
-// transpose every register mixes, so the largest bound is carried into the A' stages.
-struct InvPlanS {
-    bool red1[5][32];  // reduce register r before B' stage b
-    bool redT[32];     // ... before the transpose
-    bool red2[4][32];  // ... before the A' stage on register bit rb
-    bool red3[32];     // ... before the last stage (bit 9)
-    int fin[16];       // last-stage sum x + y: |.| < 2^fin Q -> add 2^fin Q, then fin + 1 conditional subtractions
-};
-// LIM: the bound on |x| + |y| (units of Q/10) that keeps sums below 2^31: 16 Q for Q < 2^27,
-// 8 Q for Q < 2^28
-constexpr int lim_s(bool lz) { return lz ? 160 : 80; }
-constexpr void plan_half(int (&B)[32], bool (&red)[5][32], int stages, int kLimS) {
-    for (int b = 0; b < stages; ++b)
-        for (int r = 0; r < 32; ++r) {
-            if (r & (1 << b)) continue;
-            const int s = r | (1 << b);
-            while (B[r] + B[s] > kLimS) {
-                const int e = B[r] >= B[s] ? r : s;
-                B[e]         = 10;
-                red[b][e]    = true;
-            }
-            B[r] = B[r] + B[s];
-            B[s] = 10;
-        }
-}
-template <int BIN, int kLimS>
-constexpr InvPlanS make_inv_plan() {
-    InvPlanS p{};
-    int B[32] = {};
-    for (int r = 0; r < 32; ++r) B[r] = BIN;
-    plan_half(B, p.red1, 5, kLimS);
-    int U = 0;
-    for (int r = 0; r < 32; ++r) {
-        if (B[r] > 20) {
-            p.redT[r] = true;
-            B[r]      = 10;
-        }
-        U = B[r] > U ? B[r] : U;
-    }
-    for (int r = 0; r < 32; ++r) B[r] = U;
-    bool red2[5][32] = {};
-    plan_half(B, red2, 4, kLimS);
-    for (int b = 0; b < 4; ++b)
-        for (int r = 0; r < 32; ++r) p.red2[b][r] = red2[b][r];
-    for (int r = 0; r < 16; ++r) {
-        while (B[r] + B[r | 16] > kLimS) {
-            const int e = B[r] >= B[r | 16] ? r : (r | 16);
-            B[e]        = 10;
-            p.red3[e]   = true;
-        }
-        int f = 0;
-        while ((10 << f) < B[r] + B[r | 16]) ++f;
-        p.fin[r] = f;
-    }
-    return p;
-}
+// Gentleman-Sande on signed residues (gs_bf_s) with the compile-time reduction plan of red_plan.h: here the
+// half-wave shape (in layout B' the register index is the slot's low 5 bits, so the bound of every element a
+// register holds is the same), which reduces what exceeds 2 Q before its one transpose.
 
 // One leg of the last inverse stage when the result goes straight into the digit decomposition (DEC below): no
 // canonical intermediate.  a is the leg's signed word (x + y with wR = 2^32 mod Q, or x - y with wR = TableI[1]),
@@ -416,10 +358,11 @@ FHE_DEV uint32_t dec_leg2(uint32_t x, uint32_t w1R, uint32_t y, uint32_t w2R, ui
 //   out[r|8] = u X + v Y,        out[r|24] = w1 (u X - v Y) = v X + u Y      (X = a - b, Y = c - d),
 // so the last two are two-term legs (dec_leg2) on X and Y: the products u X, v Y and w1 (..) are never formed,
 // 8 multiplies and 16 instructions for the pair instead of 12 and 22.  |a| + |b| + |c| + |d| <= 2^31 is what the
-// plan's last-stage check (sum of the two sums' bounds <= LIM) already guarantees when it placed no red3 reduction
-// on the group; a group with one takes the two stages apart as before.
-constexpr bool inv_group_ok(const InvPlanS& p, int r) {
-    return !p.red3[r] && !p.red3[r | 8] && !p.red3[r | 16] && !p.red3[r | 24];
+// plan's last-stage check (sum of the two sums' bounds <= LIM) already guarantees when its last row marks no
+// register of the group; a group with one takes the two stages apart as before.
+constexpr bool inv_group_ok(const RedPlan<HalfWaveShape>& p, int r) {
+    const bool(&last)[32] = p.red[HalfWaveShape::S - 1];
+    return !last[r] && !last[r | 8] && !last[r | 16] && !last[r | 24];
 }
 
 // B' (EVAL, |inputs| < BIN Q / 10, signed) -> A' (COEF), canonical [0, Q) like inv_pass.
@@ -428,7 +371,7 @@ constexpr bool inv_group_ok(const InvPlanS& p, int r) {
 template <int BIN, bool LZ = true, bool PRE = false, bool DEC = false>
 FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* __restrict__ twA,
                         const uint32_t* s_twB, uint32_t w1R, uint32_t oneR, const Mod& m, uint32_t cms = 0) {
-    constexpr InvPlanS P = make_inv_plan<BIN, lim_s(LZ)>();
+    constexpr RedPlan<HalfWaveShape> P = red_plan_halfwave(BIN, lim_s(LZ));
     TW_PRELOAD
 #pragma unroll
     for (int b = 0; b <= 4; ++b) {
@@ -436,17 +379,12 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << b)) continue;
             const int s = r | (1 << b);
-            if (P.red1[b][r]) v[r] = smont_mul(v[r], oneR, m);
-            if (P.red1[b][s]) v[s] = smont_mul(v[s], oneR, m);
-            const uint32_t w = TWB(b, r >> (b + 1));
-            const uint32_t x = v[r], y = v[s];
-            v[r]             = x + y;
-            v[s]             = smont_mul(x - y, w, m);
+            if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
+            if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
+            gs_bf_s(v[r], v[s], TWB(b, r >> (b + 1)), m);
         }
     }
-#pragma unroll
-    for (int r = 0; r < 32; ++r)
-        if (P.redT[r]) v[r] = smont_mul(v[r], oneR, m);
+    red_row(v, P.redT[0], oneR, m);
     transpose32(v, tile, l);
     constexpr bool GRP = DEC && FHE_INV_GROUP;
 #pragma unroll
@@ -456,13 +394,10 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
             const int s = r | (1 << rb);
-            if (P.red2[rb][r]) v[r] = smont_mul(v[r], oneR, m);
-            if (P.red2[rb][s]) v[s] = smont_mul(v[s], oneR, m);
+            if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
+            if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
             if (GRP && rb == 3 && inv_group_ok(P, r & 7)) continue;  // the group's two stages together, below
-            const uint32_t w = twA[(1 << (9 - b)) + (r >> (rb + 1))];
-            const uint32_t x = v[r], y = v[s];
-            v[r]             = x + y;
-            v[s]             = smont_mul(x - y, w, m);
+            gs_bf_s(v[r], v[s], twA[(1 << (9 - b)) + (r >> (rb + 1))], m);
         }
     }
     if (GRP) {
@@ -478,26 +413,19 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
             v[r | 24] = dec_leg2(X, vR, Y, uR, cms, m);
         }
     }
-    // bit 9 (transformnat-impl.h:599-623); its N^-1 factor is already in the data.  Signed results
-    // to [0, Q): the sum by adding 2^f Q and f + 1 conditional subtractions, the product (in
-    // (-Q, Q)) by min(d, d + Q) on the unsigned words.
+    // bit 9; canonical results (gs_last_s) unless DEC
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         if (GRP && inv_group_ok(P, r & 7)) continue;
-        if (P.red3[r]) v[r] = smont_mul(v[r], oneR, m);
-        if (P.red3[r | 16]) v[r | 16] = smont_mul(v[r | 16], oneR, m);
-        const uint32_t x = v[r], y = v[r | 16];
+        if (P.red[9][r]) v[r] = smont_mul(v[r], oneR, m);
+        if (P.red[9][r | 16]) v[r | 16] = smont_mul(v[r | 16], oneR, m);
         if (DEC) {
+            const uint32_t x = v[r], y = v[r | 16];
             v[r]      = dec_leg(x + y, oneR, cms, m);
             v[r | 16] = dec_leg(x - y, w1R, cms, m);
             continue;
         }
-        uint32_t s       = x + y + (m.Q << P.fin[r]);
-#pragma unroll
-        for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
-        const uint32_t d = smont_mul(x - y, w1R, m);
-        v[r]             = s;
-        v[r | 16]        = min(d, d + m.Q);
+        gs_last_s(v[r], v[r | 16], P.fin[r], w1R, m);
     }
 }
 
@@ -1008,76 +936,15 @@ FHE_DEV void automorphism_eval(uint32_t (&v)[32], uint32_t* region, int l, uint3
 //   C: lane L = x7..x2, register r = (x9x8) << 2 | x1x0;   B: lane = (x9..x6) << 2 | x1x0,
 //   register = x5..x2;   A: lane = x5..x0, register = x9..x6.   LDS word of x: x + 4 (x >> 6).
 FHE_DEV int wt64(int x) { return x + ((x >> 6) << 2); }
-struct InvPlanWW {
-    bool red[10][16];  // reduce register r before stage s (C bit 0, C bit 1, B bits 0..3, A bits 0..2, last)
-    bool redT[2][16];  // ... before the C -> B / B -> A transpose
-    int fin[8];        // last-stage sum: |x + y| < 2^fin Q
-    int cost;          // 2 per reduction + 1 per final conditional subtraction (their issue-cycle ratio)
-};
-// a transpose mixes every register, so the largest bound reaches all of them: registers above the
-// threshold TT[k] are reduced before transpose k (round 5; without it the A stages of the LMKCDEY
-// automorphism's inverse took 36 reductions per lane, with it 16).  make_inv_plan_ww searches the thresholds.
-template <int BIN, int LIM>
-constexpr InvPlanWW inv_plan_ww_t(int T0, int T1) {
-    InvPlanWW p{};
-    int B[16] = {};
-    for (int r = 0; r < 16; ++r) B[r] = BIN;
-    const int bits[10] = {0, 1, 0, 1, 2, 3, 0, 1, 2, 3};
-    int nred = 0;
-    for (int st = 0; st < 10; ++st) {
-        if (st == 2 || st == 6) {
-            const int k = st == 2 ? 0 : 1, T = k ? T1 : T0;
-            int U = 0;
-            for (int r = 0; r < 16; ++r) {
-                if (B[r] > T) {
-                    B[r]         = 10;
-                    p.redT[k][r] = true;
-                    ++nred;
-                }
-                U = B[r] > U ? B[r] : U;
-            }
-            for (int r = 0; r < 16; ++r) B[r] = U;
-        }
-        const int bt = bits[st];
-        for (int r = 0; r < 16; ++r) {
-            if (r & (1 << bt)) continue;
-            const int q = r | (1 << bt);
-            while (B[r] + B[q] > LIM) {
-                const int e  = B[r] >= B[q] ? r : q;
-                B[e]         = 10;
-                p.red[st][e] = true;
-                ++nred;
-            }
-            if (st == 9) {
-                int f = 0;
-                while ((10 << f) < B[r] + B[q]) ++f;
-                p.fin[r] = f;
-            }
-            B[r] = B[r] + B[q];
-            B[q] = 10;
-        }
-    }
-    p.cost = 2 * nred;
-    for (int r = 0; r < 8; ++r) p.cost += p.fin[r] + 1;
-    return p;
-}
-template <int BIN, int LIM>
-constexpr InvPlanWW make_inv_plan_ww() {
-    InvPlanWW best = inv_plan_ww_t<BIN, LIM>(kPlanT[7], kPlanT[7]);
-    for (int a = 0; a < kPlanTN; ++a)
-        for (int b = 0; b < kPlanTN; ++b) {
-            const InvPlanWW p = inv_plan_ww_t<BIN, LIM>(kPlanT[a], kPlanT[b]);
-            if (p.cost < best.cost) best = p;
-        }
-    return best;
-}
 // EVAL (layout C, |v| < BIN Q / 10) -> canonical COEF (layout A); the keys carry N^-1, so the last
 // stage scales by TableI[1] only (as inv_pass_s).  tile: 1088 words of this wave; s_tabI: TableI.
 // DEC: decompose2's d + C instead of the canonical coefficient, as inv_pass_s (the LMKCDEY automorphism)
 template <int BIN, bool LZ, bool DEC = false>
 FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t* s_tabI, uint32_t w1R,
                         uint32_t oneR, const Mod& m, uint32_t cms = 0) {
-    constexpr InvPlanWW P = make_inv_plan_ww<BIN, lim_s(LZ)>();
+    constexpr RedPlan<WaveShape> P = red_plan_search<WaveShape>(BIN, lim_s(LZ));
+    // redp / redt keep their own statements here: through red_row (boot_arith.h), k_blind_rotate_ginx2 and
+    // k_blind_rotate_lmk / _lmk3 for Q < 2^27 came out with other register numbers in their prologues
     auto redp = [&](int st) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -1088,25 +955,20 @@ FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t
         for (int r = 0; r < 16; ++r)
             if (P.redT[k][r]) v[r] = smont_mul(v[r], oneR, m);
     };
-    auto gs = [&](uint32_t& x, uint32_t& y, uint32_t w) {
-        const uint32_t t = x + y;
-        y                = smont_mul(x - y, w, m);
-        x                = t;
-    };
     const int G = L >> 2, jj = L & 3;
     redp(0);
 #pragma unroll
     for (int hh = 0; hh < 4; ++hh) {
         const uint2 w0 = *reinterpret_cast<const uint2*>(s_tabI + 512 + (hh << 7) + (L << 1));
-        gs(v[4 * hh], v[4 * hh + 1], w0.x);
-        gs(v[4 * hh + 2], v[4 * hh + 3], w0.y);
+        gs_bf_s(v[4 * hh], v[4 * hh + 1], w0.x, m);
+        gs_bf_s(v[4 * hh + 2], v[4 * hh + 3], w0.y, m);
     }
     redp(1);
 #pragma unroll
     for (int hh = 0; hh < 4; ++hh) {
         const uint32_t w1 = s_tabI[256 + (hh << 6) + L];
-        gs(v[4 * hh], v[4 * hh + 2], w1);
-        gs(v[4 * hh + 1], v[4 * hh + 3], w1);
+        gs_bf_s(v[4 * hh], v[4 * hh + 2], w1, m);
+        gs_bf_s(v[4 * hh + 1], v[4 * hh + 3], w1, m);
     }
     // C -> B
     redt(0);
@@ -1124,7 +986,7 @@ FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], s_tabI[(1 << (9 - b)) + (G << (5 - b)) + (r >> (rb + 1))]);
+            gs_bf_s(v[r], v[r | (1 << rb)], s_tabI[(1 << (9 - b)) + (G << (5 - b)) + (r >> (rb + 1))], m);
         }
     }
     // B -> A
@@ -1142,25 +1004,20 @@ FHE_DEV void inv_wave_s(uint32_t (&v)[16], uint32_t* tile, int L, const uint32_t
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             if (r & (1 << rb)) continue;
-            gs(v[r], v[r | (1 << rb)], s_tabI[(1 << (9 - b)) + (r >> (rb + 1))]);
+            gs_bf_s(v[r], v[r | (1 << rb)], s_tabI[(1 << (9 - b)) + (r >> (rb + 1))], m);
         }
     }
-    // bit 9 (transformnat-impl.h:599-623), canonical results as inv_pass_s
+    // bit 9, as inv_pass_s
     redp(9);
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-        const uint32_t x = v[r], y = v[r | 8];
         if (DEC) {
+            const uint32_t x = v[r], y = v[r | 8];
             v[r]     = dec_leg(x + y, oneR, cms, m);
             v[r | 8] = dec_leg(x - y, w1R, cms, m);
             continue;
         }
-        uint32_t s       = x + y + (m.Q << P.fin[r]);
-#pragma unroll
-        for (int f = P.fin[r]; f >= 0; --f) s = csub(s, m.Q << f);
-        const uint32_t d = smont_mul(x - y, w1R, m);
-        v[r]             = s;
-        v[r | 8]         = min(d, d + m.Q);
+        gs_last_s(v[r], v[r | 8], P.fin[r], w1R, m);
     }
 }
 // automorphism X -> X^k of both components (as automorphism_eval: every half-wave gets its own
@@ -1198,18 +1055,18 @@ FHE_DEV void automorphism_wide(uint32_t (&v)[32], uint32_t (&a0)[16], uint32_t* 
 // first stages (FHE_FWD_GROUP, see there)
 template <bool LZ> constexpr int kLmkAcc = (!LZ && FHE_FWD_TIGHT) ? (FHE_FWD_GROUP ? 24 : 22) : 20;
 // the larger bound is free: the inverse plans reduce no more often from 2.4 Q than from 2.2 Q
-constexpr int inv_plan_reds(const InvPlanS& p) {
+constexpr int halfwave_plan_reds(const RedPlan<HalfWaveShape>& p) {
     int n = 0;
     for (int r = 0; r < 32; ++r) {
-        for (int b = 0; b < 5; ++b) n += p.red1[b][r];
-        for (int b = 0; b < 4; ++b) n += p.red2[b][r];
-        n += p.redT[r] + p.red3[r];
+        for (int s = 0; s < HalfWaveShape::S; ++s) n += p.red[s][r];
+        n += p.redT[0][r];
     }
     for (int r = 0; r < 16; ++r) n += p.fin[r];
     return n;
 }
-static_assert(inv_plan_reds(make_inv_plan<24, lim_s(false)>()) == inv_plan_reds(make_inv_plan<22, lim_s(false)>()) &&
-                  make_inv_plan_ww<24, lim_s(false)>().cost == make_inv_plan_ww<22, lim_s(false)>().cost,
+static_assert(halfwave_plan_reds(red_plan_halfwave(24, lim_s(false))) ==
+                      halfwave_plan_reds(red_plan_halfwave(22, lim_s(false))) &&
+                  red_plan_search<WaveShape>(24, lim_s(false)).cost == red_plan_search<WaveShape>(22, lim_s(false)).cost,
               "kLmkAcc 24 must cost the inverse transforms nothing over 22");
 // DM: the AP/DM accumulator runs the same op loop with external products only (AddToAccDM ==
 // AddToAccLMKCDEY, rgsw-acc-dm.cpp:119-145) and no initial automorphism of acc1.

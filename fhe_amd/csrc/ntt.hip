@@ -14,6 +14,7 @@
 // written per coefficient (u64 words, as the reference stores them); all arithmetic exact mod Q.
 #include "arith.h"
 #include "ntt.h"
+#include "red_plan.h"
 
 namespace fhe_amd {
 
@@ -144,40 +145,6 @@ struct SignedA {
     }
 };
 
-// signed inverse: |x| + |y| of every butterfly must stay < 2^31 = 16 Q (units of Q/10 below);
-// before stage s (execution order: C bit 0, C bit 1, B bits 0..3, A bits 0..2, last) register r is
-// reduced to (-Q, Q) when red[s][r].  Bounds are uniform over a register within a layout and
-// become the maximum at a transpose.
-struct InvPlanW {
-    bool red[10][16];
-};
-constexpr InvPlanW make_inv_plan_w() {
-    InvPlanW p{};
-    int B[16] = {};
-    for (int r = 0; r < 16; ++r) B[r] = 10;
-    const int bits[10] = {0, 1, 0, 1, 2, 3, 0, 1, 2, 3};
-    for (int st = 0; st < 10; ++st) {
-        if (st == 2 || st == 6) {
-            int U = 0;
-            for (int r = 0; r < 16; ++r) U = B[r] > U ? B[r] : U;
-            for (int r = 0; r < 16; ++r) B[r] = U;
-        }
-        const int bt = bits[st];
-        for (int r = 0; r < 16; ++r) {
-            if (r & (1 << bt)) continue;
-            const int q = r | (1 << bt);
-            while (B[r] + B[q] > 160) {
-                const int e  = B[r] >= B[q] ? r : q;
-                B[e]         = 10;
-                p.red[st][e] = true;
-            }
-            B[r] = B[r] + B[q];
-            B[q] = 10;
-        }
-    }
-    return p;
-}
-
 // PF: a persistent wave's next polynomial is loaded during the current one (batches larger than the
 // resident grid); without it every wave transforms at most one polynomial and loads nothing more
 template <bool INV, class A, bool PF>
@@ -189,7 +156,10 @@ __global__ void __launch_bounds__(512)
     TW* s_tw        = reinterpret_cast<TW*>(smem);                            // 1024 entries
     uint32_t* tiles = reinterpret_cast<uint32_t*>(smem + 1024 * sizeof(TW));  // 8 x kWTile
     const A a0(K);
-    constexpr InvPlanW P = make_inv_plan_w();
+    // signed inverse: |x| + |y| of every butterfly must stay < 2^31 = 16 Q; before stage s (execution order: C bit 0,
+    // C bit 1, B bits 0..3, A bits 0..2, last) register r is reduced to (-Q, Q) when P.red[s][r]: red_plan.h's wave
+    // shape from canonical inputs, nothing reduced before the transposes
+    constexpr RedPlan<WaveShape> P = red_plan<WaveShape>(10, 160, kPlanNoT, kPlanNoT);
     for (int i = threadIdx.x; i < 1024; i += blockDim.x) s_tw[i] = tab[i];
 
     const int L     = threadIdx.x & 63;
@@ -306,7 +276,7 @@ __global__ void __launch_bounds__(512)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // C: stage 0 then stage 1 (GS); signed: planned reductions (InvPlanW)
+            // C: stage 0 then stage 1 (GS); signed: planned reductions (P)
             auto redp = [&](int st) {
                 if (A::kSigned) {
 #pragma unroll

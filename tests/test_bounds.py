@@ -10,6 +10,7 @@ B on its inputs to B (1 + Q/2^32) + Q/2.  From signed digits (|d| <= 2^(g-1)) th
   - K1w QM 2 (2^28 <= Q < 2^29): five stages, a reduction (float: < 0.51 Q; signed Montgomery by 2^32 mod Q:
     < B Q/2^32 + Q/2), four stages, a reduction, two stages.
 Every intermediate bound must stay below 2^31, and the inverse plans' limits (16 Q / 8 Q / 4 Q) too.
+The inverse transforms' reduction plans themselves (red_plan.h) are replayed in tests/test_red_plan.py.
 CPU-only: the moduli come from the host parameter table, the kernel choice from Params.kernel."""
 from fractions import Fraction
 
