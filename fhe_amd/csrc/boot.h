@@ -37,7 +37,15 @@ struct BootTables {
     // (Table[2] +- Table[1] Table[2]) / 2 (Montgomery): the signed forward passes' first two stages as one
     // 4-point group with two products (nt.h fwd_group_consts, bootstrap.hip fwd_group4)
     uint32_t gpR, gmR;
+    // Product twiddles of the stage pairs K1 takes as 4-point groups (nt.h stage_group_table, bootstrap.hip
+    // ct_group4_s / gs_group4_s), Montgomery form, in the allocation of twA_fwd at word offset grp from it:
+    // kGroupUniWords forward, kGroupUniWords inverse, kGroupLaneWords forward, kGroupLaneWords inverse.  0: none.
+    // A word offset in the struct's tail padding instead of four more pointers: sizeof(BootTables), and with it the
+    // argument layout of every kernel that takes one, stays what it was.
+    uint32_t grp;
 };
+constexpr int kGroupUniWords = 8, kGroupLaneWords = 320;
+static_assert(sizeof(BootTables) == 120, "BootTables is a kernel argument: its size fixes every later argument's offset");
 
 // Digit exchange between the half-waves in the external products: ds_bpermute of the other half's
 // digits, with the key rows of half 1 stored swapped in pairs (row d at position d ^ 1) so that every

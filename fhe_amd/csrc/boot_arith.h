@@ -87,6 +87,40 @@ FHE_DEV void gs_bf_s(uint32_t& x, uint32_t& y, uint32_t wR, const Mod& m) {
     y                = smont_mul(x - y, wR, m);
     x                = t;
 }
+// x w + y z as one unreduced 64-bit chain and one signed Montgomery reduction (a two-term leg): below
+// (|x| + |y|) Q 2^-32 + Q/2 in absolute value for w, z < Q
+FHE_DEV uint32_t smont_mul2(uint32_t x, uint32_t wR, uint32_t y, uint32_t zR, const Mod& m) {
+    return smont_red(mad_i64_i32((int32_t)x, (int32_t)wR, mad_i64_i32((int32_t)y, (int32_t)zR, 0)), m);
+}
+// Two signed Cooley-Tukey stages as one 4-point group: the stage on register bit hi (twiddle w1 for both pairs),
+// then the one on bit lo (w2 for the pair below hi, w3 above) on {a, b, c, d} = registers {r, r|lo, r|hi, r|hi|lo}.
+// Two radix-2 stages give a + w1 c +- w2 (b + w1 d) and a - w1 c +- w3 (b - w1 d); with the product twiddles
+// w12 = w1 w2 and w13n = -(w1 w3) (nt.h stage_group_consts) the two second-stage terms are two-term legs of b and
+// d, and w1 d is never formed: 11 multiplies and 17 instructions instead of 12 and 20.  Inputs below B give
+// outputs below B + (B e + Q/2) + (2 B e + Q/2) = (1 + 3 e) B + Q, e = Q 2^-32 (two radix-2 stages:
+// (1 + e)^2 B + (1 + e / 2) Q).
+FHE_DEV void ct_group4_s(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t w1, uint32_t w2, uint32_t w3,
+                         uint32_t w12, uint32_t w13n, const Mod& m) {
+    const uint32_t t = smont_mul(c, w1, m);
+    const uint32_t U = smont_mul2(b, w2, d, w12, m), V = smont_mul2(b, w3, d, w13n, m);
+    const uint32_t a1 = a + t, c1 = a - t;
+    a = a1 + U;
+    b = a1 - U;
+    c = c1 + V;
+    d = c1 - V;
+}
+// Two signed Gentleman-Sande stages as one group: the stage on bit lo (wa for the pair (a, b), wb for (c, d)), then
+// the one on bit hi (wg for both pairs: its index drops bit lo).  wag = wa wg, wbgn = -(wb wg).  The sums as two
+// radix-2 stages form them; the three products in (-Q, Q) when |a| + |b| + |c| + |d| <= 2^31, which the reduction
+// plan sees to (red_plan.h red_plan_group_ok).  11 multiplies and 17 instructions instead of 12 and 20.
+FHE_DEV void gs_group4_s(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t wa, uint32_t wb, uint32_t wg,
+                         uint32_t wag, uint32_t wbgn, const Mod& m) {
+    const uint32_t s1 = a + b, s2 = c + d, X = a - b, Y = c - d;
+    a = s1 + s2;
+    c = smont_mul(s1 - s2, wg, m);
+    b = smont_mul2(X, wa, Y, wb, m);
+    d = smont_mul2(X, wag, Y, wbgn, m);
+}
 // LIM of the plans: the bound on |x| + |y| (units of Q/10) that keeps sums below 2^31: 16 Q for Q < 2^27,
 // 8 Q for Q < 2^28
 constexpr int lim_s(bool lz) { return lz ? 160 : 80; }

@@ -69,6 +69,60 @@
 #ifndef FHE_INV_GROUP
 #define FHE_INV_GROUP 1
 #endif
+// K1 GINX with Q < 2^27 also takes middle stage pairs of its loop transforms as 4-point groups with product
+// twiddles (boot_arith.h ct_group4_s / gs_group4_s, BootTables::grp): three instructions and one multiply less
+// per group.  One switch per pair, named by layout and register bits in execution order (A/B each alone):
+// forward A' bits 2, 1 and B' bits 4, 3 and 2, 1; inverse B' bits 1, 2 and 3, 4 and A' bits 1, 2.  An inverse
+// group whose second stage the reduction plan marks runs as two stages (red_plan.h red_plan_group_ok): from
+// |acc| < 2.8 Q that leaves 4 of the 8 groups of B' bits 1, 2 (11 instructions less in the loop), 7 of 8 of B' bits
+// 3, 4 (19 less) and all 8 of A' bits 1, 2 (24).  A pair is kept when it takes at least 20 instructions per
+// polynomial out of the loop (three per group, less what its preloads cost): the two B' inverse pairs are off.
+// Q >= 2^27 (FM 2) takes forward A' bits 2, 1 only: with all three forward pairs the digits reach 8.0009 Q (1.5 Q
+// through B -> (1 + 3/16) B + Q and B -> (1 + 1/16) B + Q/2), with two of them the LMKCDEY accumulator passes
+// kLmkAcc (4 x 7.72 Q / 16 + Q/2 = 2.43 Q); with A' 2, 1 alone they end below 7.52 Q and |acc| below 2.38 Q
+// (fwd_groups_bound_ok).  From LIM = 8 Q the inverse plan admits 4, 6 and 4 groups of 8: below the 20
+// instructions a pair must save, none taken.
+// Which pairs a kernel takes is a mask per instantiation family (FHE_GROUPS_*), and-ed with the switches.
+#ifndef FHE_FWD_GROUP_A21
+#define FHE_FWD_GROUP_A21 1
+#endif
+#ifndef FHE_FWD_GROUP_B43
+#define FHE_FWD_GROUP_B43 1
+#endif
+#ifndef FHE_FWD_GROUP_B21
+#define FHE_FWD_GROUP_B21 1
+#endif
+#ifndef FHE_INV_GROUP_B12
+#define FHE_INV_GROUP_B12 0
+#endif
+#ifndef FHE_INV_GROUP_B34
+#define FHE_INV_GROUP_B34 0
+#endif
+#ifndef FHE_INV_GROUP_A12
+#define FHE_INV_GROUP_A12 1
+#endif
+#define FHE_GRP_FA21 1
+#define FHE_GRP_FB43 2
+#define FHE_GRP_FB21 4
+#define FHE_GRP_IB12 8
+#define FHE_GRP_IB34 16
+#define FHE_GRP_IA12 32
+// K1 GINX, Q < 2^27, half-resolution monomial table (every gate): every pair that is switched on
+#ifndef FHE_GROUPS_GINX
+#define FHE_GROUPS_GINX 63
+#endif
+// ... full-resolution table (ciphertext modulus 2N): see kGinxFullGroups
+#ifndef FHE_GROUPS_GINX_FULL
+#define FHE_GROUPS_GINX_FULL FHE_GRP_FA21
+#endif
+// the LMKCDEY / AP op-list kernel for Q < 2^27 and for Q >= 2^27: the pairs with wave-uniform twiddles (no LDS
+// table, no preloaded registers: AP / DM keeps its three waves per SIMD); Q >= 2^27 the forward one only
+#ifndef FHE_GROUPS_LMK1
+#define FHE_GROUPS_LMK1 (FHE_GRP_FA21 | FHE_GRP_IA12)
+#endif
+#ifndef FHE_GROUPS_LMK2
+#define FHE_GROUPS_LMK2 FHE_GRP_FA21
+#endif
 
 namespace fhe_amd {
 
@@ -150,6 +204,14 @@ constexpr int twb_off(int b) { return 32 * ((1 << (4 - b)) - 1); }
     if (PRE) {                                                        \
         _Pragma("unroll") for (int j = 0; j < 31; ++j) tw[j] = s_twB[j * 32 + l]; \
     }
+// the lane-major product twiddles of the grouped B' pairs (entry e of nt.h stage_group_table), preloaded alike;
+// entries no enabled pair reads are never loaded
+#define TWG(e) (PRE ? twg[e] : s_twG[(e) * 32 + l])
+#define TWG_PRELOAD(first, last)                                                               \
+    uint32_t twg[10];                                                                          \
+    if (PRE) {                                                                                 \
+        _Pragma("unroll") for (int j = (first); j < (last); ++j) twg[j] = s_twG[j * 32 + l];   \
+    }
 
 // forward NTT: A' (COEF, inputs < Q) -> B' (EVAL), outputs < 14Q (< 2^32 for Q < 2^28):
 // 5 stages (< 11Q), reduce to < 4Q at the transpose, 5 stages (< 14Q)
@@ -191,11 +253,42 @@ FHE_DEV void fwd_pass(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* 
 // are reduced to (-Q, Q), so the B' outputs stay < 6Q (a Cooley-Tukey output is bounded by |x| + Q).
 // FM 2 with FHE_FWD_TIGHT: no reduction; from the group's 3Q/2 + 2^g eight stages B -> (1 + 1/16) B + Q/2
 // reach 9.5 Q 1.0625^8 - 8Q + 1.63 2^g < 7.43Q + 2^(g+1) < 8Q (ten radix-2 stages: 6.67Q).
-template <int FM, bool PRE = false>
+// GR (FM 1 with the first group): the stage pairs of FHE_FWD_GROUP_A21 / _B43 / _B21 as ct_group4_s, product
+// twiddles from twG (uniform, 8 words) and s_twG (lane-major, 320 words).  From the first group's 3Q/2 + 2^g a
+// group takes B to (1 + 3/32) B + Q and a radix-2 stage to (1 + 1/32) B + Q/2: group, stage, group, group, stage
+// end below 6.64 Q + 2^(g+1), inside the 9.5 Q + 2^g that everything downstream of the pass is proven for.
+// FM 2 (e = Q 2^-32 <= 1/16): only A' 2, 1: group, then six stages end below 7.52 Q < 8 Q, and four such digits times
+// keys < Q keep |acc| < 4 x 7.52 Q / 16 + Q/2 < 2.38 Q inside kLmkAcc = 2.4 Q.
+// the pairs the switches allow
+// (the forward pairs follow the first group, so FHE_FWD_GROUP=0 takes them out; the inverse pairs do not depend on it)
+constexpr int kGrpSwitches = (FHE_FWD_GROUP ? (FHE_FWD_GROUP_A21 ? FHE_GRP_FA21 : 0) | (FHE_FWD_GROUP_B43 ? FHE_GRP_FB43 : 0) |
+                                                  (FHE_FWD_GROUP_B21 ? FHE_GRP_FB21 : 0)
+                                            : 0) |
+                             (FHE_INV_GROUP_B12 ? FHE_GRP_IB12 : 0) | (FHE_INV_GROUP_B34 ? FHE_GRP_IB34 : 0) |
+                             (FHE_INV_GROUP_A12 ? FHE_GRP_IA12 : 0);
+constexpr bool fwd_groups_bound_ok(int FM, int mask) {
+    // units of Q / 2^20; e = Q 2^-32 <= 1/32 (FM 1) or 1/16 (FM 2), rounded up at every step; the first group's
+    // 3Q/2 + 2^g with 2^g <= 2^10 <= Q / 2^16 (Q > 2^26): 2^4 units
+    const long long d = FM == 1 ? 32 : 16;
+    long long B = 3 * (1LL << 19) + (1LL << 4);
+    const bool grp[5] = {(mask & FHE_GRP_FA21) != 0, false, (mask & FHE_GRP_FB43) != 0, (mask & FHE_GRP_FB21) != 0, false};
+    for (int k = 0; k < 5; ++k) {
+        if (grp[k]) B = B + (3 * B + d - 1) / d + (1LL << 20);
+        else
+            for (int s = 0; s < (k == 1 || k == 4 ? 1 : 2); ++s) B = B + (B + d - 1) / d + (1LL << 19);
+    }
+    if (FM == 1) return B < 19 * (1LL << 19);  // 9.5 Q: |S| < 40 Q^2, kAccBoundLZ, the op-list kernel's 2 Q
+    // FM 2: inside 32-bit words (8 Q), and |acc| <= 4 B / 16 + Q/2 < 2.4 Q (kLmkAcc)
+    return B < 8 * (1LL << 20) && 4 * B / 16 + (1LL << 19) < 24 * (1LL << 20) / 10;
+}
+template <int FM, bool PRE = false, int GR = 0>
 FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int l,
-                       const uint32_t* __restrict__ twA, const uint32_t* s_twB, const Mod& m) {
+                       const uint32_t* __restrict__ twA, const uint32_t* s_twB, const Mod& m,
+                       const uint32_t* __restrict__ twG = nullptr, const uint32_t* s_twG = nullptr) {
     constexpr bool LZ = FM != 0;
     constexpr bool GRP = LZ && FHE_FWD_GROUP;
+    static_assert(!GR || (GRP && fwd_groups_bound_ok(FM, GR)), "grouped forward stage pairs: after the first group, |D| in bounds");
+    constexpr bool GA21 = (GR & FHE_GRP_FA21) != 0, GB43 = (GR & FHE_GRP_FB43) != 0, GB21 = (GR & FHE_GRP_FB21) != 0;
     if (GRP) {
         const uint32_t iR = twA[1];
 #pragma unroll
@@ -207,6 +300,19 @@ FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int
 #pragma unroll
     for (int b = GRP ? 7 : 9; b >= 5; --b) {
         const int rb = b - 5;
+        if (GA21 && b == 6) continue;
+        if (GA21 && b == 7) {  // stages 7 and 6 (register bits 2 and 1) together
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                if (r & 6) continue;
+                const int j = r >> 3;
+                const uint32_t w1 = twA[4 + j], w2 = twA[8 + 2 * j], w3 = twA[9 + 2 * j], w12 = twG[2 * j],
+                               w13n = twG[2 * j + 1];
+                ct_group4_s(v[r], v[r | 2], v[r | 4], v[r | 6], w1, w2, w3, w12, w13n, m);
+                ct_group4_s(u[r], u[r | 2], u[r | 4], u[r | 6], w1, w2, w3, w12, w13n, m);
+            }
+            continue;
+        }
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
@@ -237,8 +343,23 @@ FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int
         }
     }
     TW_PRELOAD
+    TWG_PRELOAD(GB43 ? 0 : 2, GB21 ? 10 : GB43 ? 2 : 0)
 #pragma unroll
     for (int b = 4; b >= 0; --b) {
+        if ((GB43 && b == 3) || (GB21 && b == 1)) continue;
+        if ((GB43 && b == 4) || (GB21 && b == 2)) {  // stages b and b - 1 together
+            const int lo = 1 << (b - 1), hi = 1 << b;
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                if (r & (lo | hi)) continue;
+                const int j = r >> (b + 1), e = b == 4 ? 0 : 2 + 2 * j;
+                const uint32_t w1 = TWB(b, j), w2 = TWB(b - 1, 2 * j), w3 = TWB(b - 1, 2 * j + 1), w12 = TWG(e),
+                               w13n = TWG(e + 1);
+                ct_group4_s(v[r], v[r | lo], v[r | hi], v[r | hi | lo], w1, w2, w3, w12, w13n, m);
+                ct_group4_s(u[r], u[r | lo], u[r | hi], u[r | hi | lo], w1, w2, w3, w12, w13n, m);
+            }
+            continue;
+        }
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << b)) continue;
@@ -255,9 +376,11 @@ FHE_DEV void fwd_pass2(uint32_t (&v)[32], uint32_t (&u)[32], uint32_t* tile, int
 }
 
 // one signed forward pass (FM 1 or 2 as in fwd_pass2): the LMKCDEY automorphism step
-template <int FM>
+// GR: the uniform pair A' bits 2, 1 only (FHE_GRP_FA21), as fwd_pass2
+template <int FM, int GR = 0>
 FHE_DEV void fwd_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* __restrict__ twA,
-                        const uint32_t* s_twB, const Mod& m) {
+                        const uint32_t* s_twB, const Mod& m, const uint32_t* __restrict__ twG = nullptr) {
+    static_assert(!(GR & ~FHE_GRP_FA21) && (!GR || (FHE_FWD_GROUP && fwd_groups_bound_ok(FM, GR))), "A' bits 2, 1 only");
     if (FHE_FWD_GROUP) {
         const uint32_t iR = twA[1];
 #pragma unroll
@@ -266,6 +389,17 @@ FHE_DEV void fwd_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
 #pragma unroll
     for (int b = FHE_FWD_GROUP ? 7 : 9; b >= 5; --b) {
         const int rb = b - 5;
+        if (GR && b == 6) continue;
+        if (GR && b == 7) {  // stages 7 and 6 (register bits 2 and 1) together
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                if (r & 6) continue;
+                const int j = r >> 3;
+                ct_group4_s(v[r], v[r | 2], v[r | 4], v[r | 6], twA[4 + j], twA[8 + 2 * j], twA[9 + 2 * j], twG[2 * j],
+                            twG[2 * j + 1], m);
+            }
+            continue;
+        }
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
@@ -368,17 +502,42 @@ constexpr bool inv_group_ok(const RedPlan<HalfWaveShape>& p, int r) {
 // B' (EVAL, |inputs| < BIN Q / 10, signed) -> A' (COEF), canonical [0, Q) like inv_pass.
 // LZ: Q < 2^27 (sums up to 16 Q), else Q < 2^28 (8 Q; the final 2^(fin+1) Q <= 16 Q < 2^32)
 // DEC: the outputs are decompose2's d + C (Dec::CmS passed as cms) instead: dec_digits takes them
-template <int BIN, bool LZ = true, bool PRE = false, bool DEC = false>
+// GR (Q < 2^27): the stage pairs of FHE_INV_GROUP_B12 / _B34 / _A12 as gs_group4_s where the plan admits the group
+// (red_plan_group_ok), product twiddles from twG (uniform, 8 words) and s_twG (lane-major, 320 words)
+template <int BIN, bool LZ = true, bool PRE = false, bool DEC = false, int GR = 0>
 FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t* __restrict__ twA,
-                        const uint32_t* s_twB, uint32_t w1R, uint32_t oneR, const Mod& m, uint32_t cms = 0) {
+                        const uint32_t* s_twB, uint32_t w1R, uint32_t oneR, const Mod& m, uint32_t cms = 0,
+                        const uint32_t* __restrict__ twG = nullptr, const uint32_t* s_twG = nullptr) {
     constexpr RedPlan<HalfWaveShape> P = red_plan_halfwave(BIN, lim_s(LZ));
+    constexpr bool GB12 = (GR & FHE_GRP_IB12) != 0, GB34 = (GR & FHE_GRP_IB34) != 0, GA12 = (GR & FHE_GRP_IA12) != 0;
+    // a two-term leg's |X| + |Y| is at most LIM Q / 10 <= 2^31 in an admitted group
+    static_assert(!GB12 || (red_plan_group_legs(P, BIN, lim_s(LZ), 1, nullptr) >= 0 &&
+                            red_plan_group_legs(P, BIN, lim_s(LZ), 1, nullptr) <= lim_s(LZ)), "B' bits 1, 2");
+    static_assert(!GB34 || (red_plan_group_legs(P, BIN, lim_s(LZ), 3, nullptr) >= 0 &&
+                            red_plan_group_legs(P, BIN, lim_s(LZ), 3, nullptr) <= lim_s(LZ)), "B' bits 3, 4");
+    static_assert(!GA12 || (red_plan_group_legs(P, BIN, lim_s(LZ), 6, nullptr) >= 0 &&
+                            red_plan_group_legs(P, BIN, lim_s(LZ), 6, nullptr) <= lim_s(LZ)), "A' bits 1, 2");
     TW_PRELOAD
+    TWG_PRELOAD(GB34 ? 0 : 2, GB12 ? 10 : GB34 ? 2 : 0)
 #pragma unroll
     for (int b = 0; b <= 4; ++b) {
+        const bool g1 = (GB12 && b == 1) || (GB34 && b == 3), g2 = (GB12 && b == 2) || (GB34 && b == 4);
 #pragma unroll
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << b)) continue;
             const int s = r | (1 << b);
+            if (g2 && red_plan_group_ok(P, b - 1, r & ~(1 << (b - 1)))) continue;  // taken with stage b - 1
+            if (g1 && red_plan_group_ok(P, b, r & ~(2 << b))) {                    // stages b and b + 1 together
+                if (r & (2 << b)) continue;
+                const int t = r | (2 << b), ts = s | (2 << b), j = r >> (b + 2), e = b == 3 ? 0 : 2 + 2 * j;
+                if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
+                if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
+                if (P.red[b][t]) v[t] = smont_mul(v[t], oneR, m);
+                if (P.red[b][ts]) v[ts] = smont_mul(v[ts], oneR, m);
+                gs_group4_s(v[r], v[s], v[t], v[ts], TWB(b, 2 * j), TWB(b, 2 * j + 1), TWB(b + 1, j), TWG(e),
+                            TWG(e + 1), m);
+                continue;
+            }
             if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
             if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
             gs_bf_s(v[r], v[s], TWB(b, r >> (b + 1)), m);
@@ -394,6 +553,18 @@ FHE_DEV void inv_pass_s(uint32_t (&v)[32], uint32_t* tile, int l, const uint32_t
         for (int r = 0; r < 32; ++r) {
             if (r & (1 << rb)) continue;
             const int s = r | (1 << rb);
+            if (GA12 && b == 7 && red_plan_group_ok(P, 6, r & ~2)) continue;  // taken with stage 6
+            if (GA12 && b == 6 && red_plan_group_ok(P, 6, r & ~4)) {          // stages 6 and 7 together
+                if (r & 4) continue;
+                const int j = r >> 3;
+                if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
+                if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
+                if (P.red[b][r | 4]) v[r | 4] = smont_mul(v[r | 4], oneR, m);
+                if (P.red[b][s | 4]) v[s | 4] = smont_mul(v[s | 4], oneR, m);
+                gs_group4_s(v[r], v[s], v[r | 4], v[s | 4], twA[8 + 2 * j], twA[9 + 2 * j], twA[4 + j], twG[2 * j],
+                            twG[2 * j + 1], m);
+                continue;
+            }
             if (P.red[b][r]) v[r] = smont_mul(v[r], oneR, m);
             if (P.red[b][s]) v[s] = smont_mul(v[s], oneR, m);
             if (GRP && rb == 3 && inv_group_ok(P, r & 7)) continue;  // the group's two stages together, below
@@ -590,9 +761,24 @@ __global__ void k_prep_ginx(F in, GateArgs g, uint16_t* __restrict__ idx, uint32
 // ---------------------------------------------------------------------------
 constexpr int kWaves = 4;
 // LZ: the monomial table holds (plain, Montgomery) pairs
-constexpr size_t boot_lds(bool full, bool lz) {
-    return (size_t)(992 * 2 + (lz ? 2 : 1) * (full ? kMonoTableWords : kMonoHalfWords) + kWaves * 2 * kTile) * 4;
+// LZ also: the lane-major product twiddles of the grouped stage pairs, both directions, behind the tiles
+// K1 with the full-resolution table holds the monomial pairs of both slots of a pair and was at 256 VGPRs with 32
+// bytes of scratch before the groups.  Every pair of K1's set took that to 44 bytes, the two pairs with wave-uniform
+// twiddles to 36; either of those alone leaves it at 32, so it takes the forward one (48 instructions, the inverse
+// one is 24).
+constexpr int kGinxHalfGroups = FHE_GROUPS_GINX & kGrpSwitches, kGinxFullGroups = FHE_GROUPS_GINX_FULL & kGrpSwitches;
+constexpr int kGrpLane = FHE_GRP_FB43 | FHE_GRP_FB21 | FHE_GRP_IB12 | FHE_GRP_IB34;  // the pairs with lane-major twiddles
+constexpr int ginx_groups(bool full, bool lz) { return !lz ? 0 : full ? kGinxFullGroups : kGinxHalfGroups; }
+// words of LDS for the lane-major product twiddles: the forward table, and the inverse one behind it if a pair reads it
+constexpr int ginx_group_lds(bool full, bool lz) {
+    const int g = ginx_groups(full, lz);
+    return (g & (FHE_GRP_IB12 | FHE_GRP_IB34)) ? 2 * kGroupLaneWords : (g & kGrpLane) ? kGroupLaneWords : 0;
 }
+constexpr size_t boot_lds(bool full, bool lz) {
+    return (size_t)(992 * 2 + (lz ? 2 : 1) * (full ? kMonoTableWords : kMonoHalfWords) + kWaves * 2 * kTile +
+                    ginx_group_lds(full, lz)) * 4;
+}
+static_assert(2 * boot_lds(true, true) <= 160 * 1024, "two K1 workgroups per CU (FHE_WAVES_PER_EU 2) in 160 KB of LDS");
 
 // MFULL: full-resolution monomial table (ciphertext modulus 2N, any exponent); otherwise the
 // half-resolution table (even exponents: every gate), where slots r and r ^ 1 share a monomial
@@ -619,6 +805,15 @@ __global__ void __launch_bounds__(256, FHE_WAVES_PER_EU)
         s_twBf[i] = T.twB_fwd[i];
         s_twBi[i] = T.twB_inv[i];
     }
+    // stage groups (LZ): uniform product twiddles through the scalar cache like twAf / twAi, lane-major ones in LDS
+    constexpr int GR = ginx_groups(MFULL, LZ);
+    // (null where this instantiation takes no pair that reads them: never dereferenced there)
+    const uint32_t* twGf = GR ? twAf + T.grp : nullptr;
+    const uint32_t* twGi = GR ? twGf + kGroupUniWords : nullptr;
+    uint32_t* s_twGf = (GR & kGrpLane) ? s_tile + kWaves * 2 * kTile : nullptr;
+    uint32_t* s_twGi = (GR & (FHE_GRP_IB12 | FHE_GRP_IB34)) ? s_twGf + kGroupLaneWords : nullptr;
+    if (GR & kGrpLane)
+        for (int i = threadIdx.x; i < ginx_group_lds(MFULL, LZ); i += 256) s_twGf[i] = twGf[2 * kGroupUniWords + i];
     {
         const uint32_t* src = mfull ? T.mono_full : T.mono;
         const uint32_t* srp = mfull ? T.monoP_full : T.monoP;
@@ -686,7 +881,9 @@ __global__ void __launch_bounds__(256, FHE_WAVES_PER_EU)
 #pragma unroll
         for (int r = 0; r < 32; ++r) dA[r] = acc[r];
         constexpr bool TAIL = LZ && FHE_DEC_TAIL;  // the inverse pass ends on d + C (dec_leg), not on [0, Q)
-        if (LZ) inv_pass_s<kAccBoundLZ, true, true, TAIL>(dA, tile, l, twAi, s_twBi, T.w1R, T.oneR, m, dec.CmS);
+        if (LZ)
+            inv_pass_s<kAccBoundLZ, true, true, TAIL, GR>(dA, tile, l, twAi, s_twBi, T.w1R, T.oneR, m, dec.CmS, twGi,
+                                                          s_twGi);
         else inv_pass(dA, tile, l, T.twA_inv, s_twBi, T.w1R, m);
         // --- SignedDigitDecompose (rgsw-acc.cpp:54-91): drop the lowest signed digit,
         //     keep the next two.  Half h decomposes acc_h: dA = D_h, dB = D_{2+h}.
@@ -696,7 +893,7 @@ __global__ void __launch_bounds__(256, FHE_WAVES_PER_EU)
             else decompose2<LZ>(dA[r], dec, dA[r], dB[r]);
         }
         // --- NTT of the four digit polynomials (two per pass, one per half)
-        fwd_pass2<LZ ? 1 : 0, true>(dA, dB, tile, l, twAf, s_twBf, m);
+        fwd_pass2<LZ ? 1 : 0, true, GR & 7>(dA, dB, tile, l, twAf, s_twBf, m, twGf, s_twGf);
         // --- external product + CMUX, slot by slot.  Lane (h, l) owns slots
         //     l*32 + r of component h; its keys are 16-byte vectors (4 slots) laid
         //     out so that each load instruction reads 1 KiB contiguous.
@@ -852,6 +1049,7 @@ hipError_t launch_blind_rotate_ginx(const GateArgs& g, const BootTables& t, cons
     const uint2* k = reinterpret_cast<const uint2*>(bsk);
     const bool lz  = t.Q < (1u << 27);
     const bool full = g.ctmod == 2 * g.N;
+    if (ginx_groups(full, lz) && !t.grp) return hipErrorInvalidValue;  // tables without the groups' product twiddles
 #define FHE_LAUNCH_GINX(MF, LZ_, IO)                                                                        \
     hipLaunchKernelGGL((k_blind_rotate_ginx<MF, LZ_, IO>), dim3(blocks), dim3(256), boot_lds(MF, LZ_), s, g, t, k, \
                        idx, tvb, ext_a, ext_b, t.twA_fwd, t.twA_inv)
@@ -1142,6 +1340,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
         const uint32_t* twAf = T.twA_fwd;
         const uint32_t* twAi = T.twA_inv;
         asm volatile("" : "+s"(twAf), "+s"(twAi));
+        // stage groups: the pairs with wave-uniform product twiddles only (FHE_GROUPS_LMK1 / _LMK2)
+        constexpr int GR = (LZ ? FHE_GROUPS_LMK1 : FHE_GROUPS_LMK2) & kGrpSwitches;
+        static_assert(!(GR & kGrpLane), "the op-list kernel has no LDS table of lane-major product twiddles");
+        const uint32_t* twGf = GR ? twAf + T.grp : nullptr;
+        const uint32_t* twGi = GR ? twGf + kGroupUniWords : nullptr;
 #if FHE_LMK_OPAQUE
         // the lane index and the wave's LDS regions made opaque per op as well: every per-lane address
         // of the op body is then derived inside it instead of being hoisted as a loop-invariant VGPR
@@ -1161,14 +1364,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
             uint4 kq[KPF + 1][4];
 #pragma unroll
             for (int r = 0; r < 32; ++r) dA[r] = acc[r];
-            inv_pass_s<kLmkAcc<LZ>, LZ, !DM && FHE_LMK_PRE, FHE_DEC_TAIL>(dA, tile, l, twAi, s_twBi, T.w1R, m.oneR, m,
-                                                                          dec.CmS);
+            inv_pass_s<kLmkAcc<LZ>, LZ, !DM && FHE_LMK_PRE, FHE_DEC_TAIL, GR>(dA, tile, l, twAi, s_twBi, T.w1R, m.oneR, m,
+                                                                              dec.CmS, twGi);
 #pragma unroll
             for (int r = 0; r < 32; ++r) {
                 if (FHE_DEC_TAIL) dec_digits<true>(dA[r], dec, dA[r], dB[r]);
                 else decompose2<true>(dA[r], dec, dA[r], dB[r]);
             }
-            fwd_pass2<FM, !DM && FHE_LMK_PRE>(dA, dB, tile, l, twAf, s_twBf, m);
+            fwd_pass2<FM, !DM && FHE_LMK_PRE, GR & 7>(dA, dB, tile, l, twAf, s_twBf, m, twGf);
             // one 16-byte vector per digit row and 4 slots (boot.h row_off)
 #pragma unroll
             for (int p = 0; p < KPF; ++p)
@@ -1253,7 +1456,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DM ? F
                 wave_lds_sync();
 #endif
             }
-            fwd_pass_s<FM>(dA, tile, l, twAf, s_twBf, m);  // half 0: EVAL digit A, half 1: EVAL digit B
+            fwd_pass_s<FM, GR & 7>(dA, tile, l, twAf, s_twBf, m, twGf);  // half 0: EVAL digit A, half 1: EVAL digit B
             const uint4* kb4 = reinterpret_cast<const uint4*>(autok) + (size_t)((FHE_LMK_ABL & 2) ? 0u : t) * (2 * 8 * 64);
             constexpr int AKPF = FHE_LMK_AKPF;
             uint4 ka[AKPF + 1][2];
@@ -1530,6 +1733,7 @@ hipError_t launch_blind_rotate_lmk(const GateArgs& g, const BootTables& t, const
     const uint2* ak = reinterpret_cast<const uint2*>(autok);
     const bool lz   = t.Q < (1u << 27);
     if (t.Q >= (1u << 28)) return hipErrorInvalidValue;  // signed residue bounds
+    if (((lz ? FHE_GROUPS_LMK1 : FHE_GROUPS_LMK2) & kGrpSwitches) && !t.grp) return hipErrorInvalidValue;
 #define FHE_LAUNCH_LMK(DM_, LZ_, IO)                                                                          \
     hipLaunchKernelGGL((k_blind_rotate_lmk<DM_, LZ_, IO>), dim3(blocks), dim3(256), lds, s, g, t, k, ak, ops, nops, \
                        maxops, tvb, ext_a, ext_b)

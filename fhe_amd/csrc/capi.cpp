@@ -867,6 +867,23 @@ int fhe_hip_fwd_group_consts(uint64_t Q, uint64_t t1, uint64_t t2, uint64_t t3, 
     return FHE_HIP_OK;
 }
 
+int fhe_hip_stage_group_consts(uint64_t Q, uint64_t t1, uint64_t w1, uint64_t w2, uint64_t w3, uint64_t* w12,
+                               uint64_t* w13n) {
+    if (!w12 || !w13n) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (!stage_group_consts(Q, t1, w1, w2, w3, w12, w13n))
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "Table[2k]^2 != Table[k] or Table[2k+1] != Table[1] * Table[2k] mod Q");
+    return FHE_HIP_OK;
+}
+
+int fhe_hip_stage_group_table(uint64_t Q, const uint64_t* table, size_t n, uint64_t* out, size_t out_cap) {
+    if (!table || !out) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
+    if (n != 1024 || out_cap < (size_t)(kGroupUniWords + kGroupLaneWords))
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "stage_group_table: a table of 1024 entries and room for 328 products");
+    if (!stage_group_table(Q, table, out))
+        return fail(FHE_HIP_ERR_INVALID_PARAM, "Table[2k]^2 != Table[k] or Table[2k+1] != Table[1] * Table[2k] mod Q");
+    return FHE_HIP_OK;
+}
+
 int fhe_hip_unpack_keys(int paramset, int method, const uint8_t* bsk_packed, size_t bsk_size, uint64_t* bsk,
                         size_t bsk_cap, const uint8_t* ksk_packed, size_t ksk_size, uint64_t* kskA, size_t kskA_cap,
                         uint64_t* kskB, size_t kskB_cap) {

@@ -178,7 +178,8 @@ void Engine::build_tables() {
     const uint64_t Q = p_.Q;
     HostNtt h;
     h.init(p_.N, Q, p_.psi);
-    std::vector<uint32_t> t(32 + 32 + 992 + 992 + 2 * (kMonoHalfWords + kMonoTableWords) + 2048, 0);
+    constexpr size_t kGroupOff = 32 + 32 + 992 + 992 + 2 * (kMonoHalfWords + kMonoTableWords) + 2048;
+    std::vector<uint32_t> t(kGroupOff + 2 * (kGroupUniWords + kGroupLaneWords), 0);
     uint32_t* twAf = t.data();
     uint32_t* twAi = twAf + 32;
     uint32_t* twBf = twAi + 32;
@@ -205,6 +206,21 @@ void Engine::build_tables() {
     uint64_t ip = 0, im = 0;
     if (!fwd_group_consts(Q, h.tabI[1], h.tabI[2], h.tabI[3], &ip, &im))
         throw std::invalid_argument("build_tables: TableI[3] != TableI[1] * TableI[2] (or TableI[1]^2 != -1) mod Q");
+    // the product twiddles of the grouped stage pairs (BootTables::grp), appended: every other block stays where it was
+    if (p_.N == 1024) {
+        uint64_t gf[kGroupUniWords + kGroupLaneWords], gi[kGroupUniWords + kGroupLaneWords];
+        if (!stage_group_table(Q, h.tab.data(), gf) || !stage_group_table(Q, h.tabI.data(), gi))
+            throw std::invalid_argument("build_tables: Table[2k] ^ 2 != Table[k] or Table[2k + 1] != Table[1] * Table[2k] mod Q");
+        uint32_t* g = t.data() + kGroupOff;
+        for (int i = 0; i < kGroupUniWords; ++i) {
+            g[i] = to_mont(gf[i], Q);
+            g[kGroupUniWords + i] = to_mont(gi[i], Q);
+        }
+        for (int i = 0; i < kGroupLaneWords; ++i) {
+            g[2 * kGroupUniWords + i] = to_mont(gf[kGroupUniWords + i], Q);
+            g[2 * kGroupUniWords + kGroupLaneWords + i] = to_mont(gi[kGroupUniWords + i], Q);
+        }
+    }
     // lane-major tables of the stages on bits 4..0 (bootstrap.hip, twb_off)
     for (int b = 4; b >= 0; --b) {
         const int per = 1 << (4 - b), off = 32 * (per - 1);
@@ -257,6 +273,7 @@ void Engine::build_tables() {
     tabs_.nR = to_mont(p_.N, Q);
     tabs_.gpR = to_mont(gp, Q);
     tabs_.gmR = to_mont(gm, Q);
+    tabs_.grp = p_.N == 1024 ? (uint32_t)kGroupOff : 0u;
 }
 
 // logGen of rgsw-cryptoparameters.cpp:115-127 (k_prep_lmk_w's group positions)

@@ -117,4 +117,65 @@ constexpr RedPlan<HalfWaveShape> red_plan_halfwave(int BIN, int LIM) {
     return red_plan<HalfWaveShape>(BIN, LIM, 20, kPlanNoT);
 }
 
+// Stage pairs as 4-point groups (bootstrap.hip gs_group4_s).  Stages st and st + 1 (register bits lo and hi, no
+// transpose between them) on {a, b, c, d} = registers {r, r | lo, r | hi, r | lo | hi} give
+//   a + b + c + d,   ((a + b) - (c + d)) w,   X u + Y v,   X u' - Y v'      (X = a - b, Y = c - d).
+// The products X u and Y v of stage st are never formed, so stage st + 1 cannot reduce them, and the two-term
+// outputs are below (|X| + |Y|) Q 2^-32 + Q/2 <= Q only for |X| + |Y| <= 2^31.  A mark of stage st + 1 never falls
+// on the product registers r | lo and r | hi | lo (their pair is 10 + 10 <= LIM); one on r or r | hi means that
+// |a| + |b| + |c| + |d| may pass LIM, and then |X| + |Y| may too.  So the plan is kept as it is (the same marks, the
+// same bounds: a two-term output counts as 10 like a product) and a group is taken as one exactly when stage
+// st + 1 marks none of its registers -- then LIM Q / 10 <= 2^31 bounds |X| + |Y| as well; the others run their
+// two stages apart.  Not built: a planner of its own for the grouped shape, which resets inputs until every group
+// qualifies and counts a two-term output as 10 where this one counts 10 + 10.  From 2.8 Q and LIM 16 Q it places 22
+// resets instead of 19 and takes all 24 groups of the three inverse pairs instead of 19, 6 instructions fewer
+// in all (tests/red_plan_groups_check.cpp prints both); for the pair the kernels take (A' bits 1, 2: every group
+// admitted as it is) the two are the same.
+template <class Sh>
+constexpr bool red_plan_group_ok(const RedPlan<Sh>& p, int st, int r) {
+    const int lo = 1 << Sh::bit[st], hi = 1 << Sh::bit[st + 1];
+    const bool(&row)[Sh::R] = p.red[st + 1];
+    return !row[r] && !row[r | lo] && !row[r | hi] && !row[r | lo | hi];
+}
+// The largest |X| + |Y| (units of Q / 10) over the two-term legs of the groups of stages st, st + 1 that
+// red_plan_group_ok admits, and the number of those groups, by replaying the plan's bounds from BIN; -1 if a
+// butterfly's |x| + |y| passes LIM anywhere in the replay (a plan made for other inputs)
+template <class Sh>
+constexpr int red_plan_group_legs(const RedPlan<Sh>& p, int BIN, int LIM, int st, int* groups) {
+    int B[Sh::R] = {};
+    for (int r = 0; r < Sh::R; ++r) B[r] = BIN;
+    int worst = 0, n = 0;
+    for (int s = 0; s < Sh::S; ++s) {
+        for (int k = 0; k < 2; ++k) {
+            if (s != Sh::tr[k]) continue;
+            int U = 0;
+            for (int r = 0; r < Sh::R; ++r) {
+                if (p.redT[k][r]) B[r] = 10;
+                U = B[r] > U ? B[r] : U;
+            }
+            for (int r = 0; r < Sh::R; ++r) B[r] = U;
+        }
+        const int bt = 1 << Sh::bit[s];
+        for (int r = 0; r < Sh::R; ++r)
+            if (p.red[s][r]) B[r] = 10;
+        if (s == st) {
+            const int hi = 1 << Sh::bit[st + 1];
+            for (int r = 0; r < Sh::R; ++r) {
+                if ((r & bt) || (r & hi) || !red_plan_group_ok(p, st, r)) continue;
+                const int legs = B[r] + B[r | bt] + B[r | hi] + B[r | bt | hi];
+                worst = legs > worst ? legs : worst;
+                ++n;
+            }
+        }
+        for (int r = 0; r < Sh::R; ++r) {
+            if (r & bt) continue;
+            if (B[r] + B[r | bt] > LIM) return -1;
+            B[r] += B[r | bt];
+            B[r | bt] = 10;
+        }
+    }
+    if (groups) *groups = n;
+    return worst;
+}
+
 }  // namespace fhe_amd

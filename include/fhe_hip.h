@@ -583,6 +583,15 @@ int fhe_hip_device_memory(int device, size_t* free_bytes, size_t* total_bytes);
  * c+- = (t2 +- t1 t2) / 2 mod Q of its first 4-point group.  FHE_HIP_ERR_INVALID_PARAM unless t1^2 = -1 and
  * t3 = t1 t2 mod Q -- the check the context's table builder makes before any kernel can run. */
 int fhe_hip_fwd_group_consts(uint64_t Q, uint64_t t1, uint64_t t2, uint64_t t3, uint64_t* c_plus, uint64_t* c_minus);
+/* Product twiddles of two transform stages the fused accumulator kernel takes as one 4-point group (host only):
+ * with t1 = Table[1], w1 = Table[k], w2 = Table[2k], w3 = Table[2k + 1] (plain residues), w12 = w1 w2 and
+ * w13n = -(w1 w3) mod Q.  FHE_HIP_ERR_INVALID_PARAM unless t1^2 = -1, w2^2 = w1 and w3 = t1 w2 mod Q.
+ * fhe_hip_stage_group_table: the 328 products of one direction from its bit-reversed table of n = 1024 entries,
+ * 8 wave-uniform ones, then 10 x 32 lane-major ones, in the order the table builder uploads them; refused as soon
+ * as one triple fails the check above. */
+int fhe_hip_stage_group_consts(uint64_t Q, uint64_t t1, uint64_t w1, uint64_t w2, uint64_t w3, uint64_t* w12,
+                               uint64_t* w13n);
+int fhe_hip_stage_group_table(uint64_t Q, const uint64_t* table, size_t n, uint64_t* out, size_t out_cap);
 /* message of the last error on this host thread */
 const char* fhe_hip_last_error(void);
 
