@@ -67,6 +67,11 @@ class _Params(ctypes.Structure):
                [(f, ctypes.c_uint64) for f in ("Q", "psi", "qKS", "bsk_words", "ksk_rows")]
 
 
+class _KeygenPlan(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("on_device", "keys")] + \
+               [(f, ctypes.c_uint64) for f in ("row_pairs", "ntt_polys", "ksk_rows", "scratch_bytes")]
+
+
 def _setup(L):
     if getattr(L, "_binfhe_ready", False):
         return L
@@ -108,6 +113,7 @@ def _setup(L):
     L.fhe_hip_eval_decomp_batch.argtypes = [vp, sz, vp, vp, u64, vp, vp]
     L.fhe_hip_bootstrap_func_batch.argtypes = [vp, sz, vp, vp, ctypes.c_uint32, vp, u64, vp, vp]
     L.fhe_hip_btkeygen_device.argtypes = [vp, vp, sz, u64, vp, vp, vp]
+    L.fhe_hip_keygen_plan_get.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_KeygenPlan)]
     L.fhe_hip_keygen_secret.argtypes = [ctypes.c_int, ctypes.c_int, u64, vp]
     L.fhe_hip_load_keys_cereal.argtypes = [vp, vp, sz, vp, sz]
     L.fhe_hip_cereal_read_keys.argtypes = [ctypes.c_int, ctypes.c_int, vp, sz, vp, sz, vp, vp, vp]
@@ -218,6 +224,25 @@ def params(paramset, method):
     p = _Params()
     check(L().fhe_hip_params_get(paramset, method, ctypes.byref(p)))
     return Params(**{f: int(getattr(p, f)) for f, _ in _Params._fields_})
+
+
+@dataclass(frozen=True)
+class KeygenPlan:
+    on_device: int
+    keys: int
+    row_pairs: int
+    ntt_polys: int
+    ksk_rows: int
+    scratch_bytes: int
+
+
+def keygen_plan(paramset, method):
+    """what device BTKeyGen does for (paramset, method) (fhe_hip_keygen_plan_get; host only): whether the keys are
+    generated on the device, the keys of the map (1, or 3 with timeOptimization), the RGSW row pairs drawn, the
+    polynomials handed to the NTT, the switching-key rows and the generator's peak device scratch in bytes"""
+    k = _KeygenPlan()
+    check(L().fhe_hip_keygen_plan_get(paramset, method, ctypes.byref(k)))
+    return KeygenPlan(**{f: int(getattr(k, f)) for f, _ in _KeygenPlan._fields_})
 
 
 def kernel_path(paramset, method):

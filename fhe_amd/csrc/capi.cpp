@@ -15,6 +15,7 @@
 #include "cereal.h"
 #include "multi.h"
 #include "keygen.h"
+#include "keygen_desc.h"
 #include "ntt.h"
 #include "nt.h"
 #include "boot.h"
@@ -345,6 +346,16 @@ int fhe_hip_btkeygen_device(fhe_hip_ctx* ctx, const uint64_t* sk, size_t n, uint
                             uint64_t* kskA, uint64_t* kskB) {
     if (!ctx || !sk) return fail(FHE_HIP_ERR_NULL_PTR, "null argument");
     return guarded([&]() -> int { ctx->eng.keygen_device(sk, n, seed, bsk, kskA, kskB); return FHE_HIP_OK; });
+}
+
+int fhe_hip_keygen_plan_get(int paramset, int method, fhe_hip_keygen_plan* out) {
+    return guarded([&]() -> int {
+        if (!out) return fail(FHE_HIP_ERR_NULL_PTR, "out is null");
+        const KeygenPlan k = keygen_plan(make_params(paramset, method));
+        out->on_device = k.on_device; out->keys = k.keys; out->row_pairs = k.row_pairs; out->ntt_polys = k.ntt_polys;
+        out->ksk_rows = k.ksk_rows; out->scratch_bytes = k.scratch_bytes;
+        return FHE_HIP_OK;
+    });
 }
 
 static bool io_ok(size_t count, const void* a, const void* b, const void* c, const void* d, const void* e,

@@ -100,8 +100,11 @@ public:
     // raw reference layouts (see include/fhe_hip.h)
     void load_bsk(const uint64_t* bsk, size_t words);
     void load_ksk(const uint64_t* A, size_t nA, const uint64_t* B, size_t nB);
-    // BTKeyGen on this device (keygen_dev.hip): keys bit-identical to keygen_bootstrap(sk, seed),
-    // generated in place in the resident layouts; non-null host pointers receive the raw layouts
+    // BTKeyGen on this device for every parameter set (keygen_dev.hip: the N = 1024, digitsG = 3 fast path;
+    // keygen_dev_wide.hip: every other set, the large-precision family and its timeOptimization map): keys
+    // bit-identical to keygen_bootstrap(sk, seed), generated in place in the resident layouts this context's
+    // kernels read; the host generator is never run.  Non-null host pointers receive the raw layouts (with
+    // timeOptimization the concatenated sizes load_ksk expects).  On failure no key stays resident.
     void keygen_device(const uint64_t* sk, size_t n, uint64_t seed, uint64_t* bsk_out, uint64_t* kskA_out,
                        uint64_t* kskB_out);
     // the resident keys of another context of the same parameter set (any device): every packed key buffer
@@ -286,6 +289,8 @@ private:
     void host_columns(size_t count, uint32_t k, const uint64_t* const* a, const uint64_t* const* b, bool staged_out,
                       uint64_t* a_out, uint64_t* b_out, Run&& run);
     void ensure_work(size_t count);
+    void keygen_device_wide(const std::vector<uint64_t>& sk, uint64_t seed, uint64_t* bsk_out, uint64_t* kskA_out,
+                            uint64_t* kskB_out);
     void build_tables();
     void build_tables_wide();
     void build_loggen();

@@ -576,14 +576,10 @@ void Engine::keygen_device(const uint64_t* sk, size_t n, uint64_t seed, uint64_t
     if (!sk) throw std::invalid_argument("secret key is null");
     if (n != p_.n) throw std::invalid_argument("secret key has wrong length");
     const std::vector<uint64_t> s(sk, sk + n);
-    if (flags_.wide) {  // large-precision family: the host generator (keygen.cpp), then the upload
-        KeySet ks;
-        keygen_bootstrap(p_, s, seed, ks);
-        load_bsk(ks.bsk.data(), ks.bsk.size());
-        load_ksk(ks.kskA.data(), ks.kskA.size(), ks.kskB.data(), ks.kskB.size());
-        if (bsk_out) std::copy(ks.bsk.begin(), ks.bsk.end(), bsk_out);
-        if (kskA_out) std::copy(ks.kskA.begin(), ks.kskA.end(), kskA_out);
-        if (kskB_out) std::copy(ks.kskB.begin(), ks.kskB.end(), kskB_out);
+    if (flags_.wide) {  // every set outside the fast path (keygen_dev_wide.hip)
+        for (uint64_t v : s)
+            if (v >= p_.qKS) throw std::invalid_argument("secret key not reduced mod qKS");
+        keygen_device_wide(s, seed, bsk_out, kskA_out, kskB_out);
         return;
     }
     const size_t words = p_.bsk_words(), rows = p_.ksk_rows();
@@ -616,6 +612,80 @@ void Engine::keygen_device(const uint64_t* sk, size_t n, uint64_t seed, uint64_t
                                              : (size_t)p_.n;
     d_autok_ = d_bsk_.as<uint32_t>() + nrgsw * p_.digitsG2 * 2 * p_.N;
     repack_ginx2();
+}
+
+// The 64-bit path's keys generated in place: one pass of keygen_bootstrap_device_wide per key of the map (one
+// without timeOptimization), each into its slice of the resident buffers, then the split kernels' second layout
+// repacked on the device.  No host buffer of a key's size exists unless the caller asked for the export; the
+// switching key's export is read back from d_wksk_, which holds the raw values.
+void Engine::keygen_device_wide(const std::vector<uint64_t>& sk, uint64_t seed, uint64_t* bsk_out, uint64_t* kskA_out,
+                                uint64_t* kskB_out) {
+    const size_t words = p_.bsk_words(), rows = p_.ksk_rows(), n = p_.n, keys = p_.ksk_keys();
+    const size_t wb = flags_.narrow ? 4 : 8, one = rows * (n + 1), W = ksk_width(p_.n);
+    sync_streams();  // nothing still reads the keys that are replaced
+    FHE_HIP_CHECK(hipSetDevice(device_));
+    auto drop = [&] {
+        d_bsk_.release();
+        d_bsk2_.release();
+        d_ksk_.release();
+        d_ksk32_.release();
+        d_wksk_.release();
+        d_autok_ = nullptr;
+    };
+    drop();
+    DevBuf raw;  // the raw bootstrapping key, when the caller asked for it
+    try {
+        d_bsk_.alloc(device_, words * wb);
+        FHE_HIP_CHECK(hipMemsetAsync(d_bsk_, 0, words * wb, stream_));  // AP: the j = 0 slots stay zero
+        d_wksk_.alloc(device_, keys * one * 8);
+        if (flags_.ks32w) {
+            d_ksk32_.alloc(device_, rows * W * 4);
+            FHE_HIP_CHECK(hipMemsetAsync(d_ksk32_, 0, rows * W * 4, stream_));
+        } else if (flags_.ks32) {
+            d_ksk_.alloc(device_, rows * W * 2);
+            FHE_HIP_CHECK(hipMemsetAsync(d_ksk_, 0, rows * W * 2, stream_));
+        }
+        if (bsk_out) {
+            raw.alloc(device_, words * 8);
+            FHE_HIP_CHECK(hipMemsetAsync(raw.as<>(), 0, words * 8, stream_));
+        }
+        auto one_key = [&](const Params& pb, uint64_t sb, size_t off, size_t k) {
+            KgWideOut o;
+            o.bsk = d_bsk_.as<char>() + off * wb;
+            o.narrow = flags_.narrow;
+            o.wksk = d_wksk_ + k * one;
+            o.ksk32 = d_ksk32_;  // ks32 / ks32w sets hold one key (no timeOptimization)
+            o.ksk16 = d_ksk_;
+            o.raw_bsk = bsk_out ? raw.as<uint64_t>() + off : nullptr;
+            keygen_bootstrap_device_wide(pb, sk, sb, device_, o, stream_);
+        };
+        if (p_.timeopt) {  // the three-key map, seeded per base as the host generator seeds it (keygen.cpp)
+            for (uint32_t bg : kSignBases) {
+                Params pb = p_.with_base(bg);
+                pb.timeopt = false;
+                one_key(pb, bg == p_.baseG ? seed : seed ^ ((uint64_t)bg * kRngGamma), p_.bsk_offset(bg), p_.ksk_index(bg));
+            }
+        } else {
+            one_key(p_, seed, 0, 0);
+        }
+        if (flags_.g3 || flags_.n2k) {
+            const KgRepackSizes z = keygen_repack_sizes(p_, flags_.g3);
+            const size_t nauto = p_.method == M_LMKCDEY ? (size_t)p_.numAutoKeys + 1 : 0;
+            d_bsk2_.alloc(device_, (n * z.per + nauto * z.aper) * 4);
+            keygen_repack_device(p_, flags_.g3, flags_.narrow, d_bsk_.as<>(), d_bsk2_.as<uint32_t>(), stream_);
+        }
+        FHE_HIP_CHECK(hipStreamSynchronize(stream_));
+        if (bsk_out) FHE_HIP_CHECK(hipMemcpy(bsk_out, raw.as<>(), words * 8, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < keys; ++k) {
+            if (kskA_out)
+                FHE_HIP_CHECK(hipMemcpy(kskA_out + k * rows * n, d_wksk_ + k * one, rows * n * 8, hipMemcpyDeviceToHost));
+            if (kskB_out)
+                FHE_HIP_CHECK(hipMemcpy(kskB_out + k * rows, d_wksk_ + k * one + rows * n, rows * 8, hipMemcpyDeviceToHost));
+        }
+    } catch (...) {
+        drop();
+        throw;
+    }
 }
 
 }  // namespace fhe_amd

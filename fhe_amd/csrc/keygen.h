@@ -96,6 +96,32 @@ void keygen_bootstrap(const Params& p, const std::vector<uint64_t>& sk, uint64_t
 void keygen_bootstrap_device(const Params& p, const std::vector<uint64_t>& sk, uint64_t seed, int device,
                              uint32_t* d_bsk, uint16_t* d_ksk, uint64_t* raw_bsk, uint64_t* raw_kskA,
                              uint64_t* raw_kskB, void* stream);
+// The same for every other set (keygen_dev_wide.hip): one key (p.timeopt ignored: the caller passes with_base(bg)
+// and the key's seed per base of the map), written into the 64-bit path's resident layouts.
+struct KgWideOut {
+    void* bsk = nullptr;          // this key's words of d_bsk_: raw order, x 2^64 mod Q (u64) or x 2^32 mod Q (u32, narrow);
+                                  // zeroed by the caller (AP's j = 0 slots are never written)
+    bool narrow = false;
+    uint64_t* wksk = nullptr;     // this key's A [rows][n] ++ B [rows]
+    uint32_t* ksk32 = nullptr;    // u32 rows of ksk_width(n), zeroed by the caller (or null)
+    uint16_t* ksk16 = nullptr;    // u16 rows of ksk_width(n), zeroed by the caller (or null)
+    uint64_t* raw_bsk = nullptr;  // this key's raw words, zeroed by the caller (or null)
+};
+void keygen_bootstrap_device_wide(const Params& p, const std::vector<uint64_t>& sk, uint64_t seed, int device,
+                                  const KgWideOut& out, void* stream);
+// The split kernels' second key layouts (Engine::pack_ginx3 when g3, else Engine::pack_n2k) from the resident
+// d_bsk_ of keygen_bootstrap_device_wide, on the device: words per index / per automorphism key, and the repack
+// (asynchronous on stream; d_bsk2 holds n * per + (LMKCDEY: numAutoKeys + 1) * aper u32 words)
+struct KgRepackSizes {
+    size_t per, aper;
+};
+inline KgRepackSizes keygen_repack_sizes(const Params& p, bool g3) {
+    const bool lmk = p.method == M_LMKCDEY;
+    const size_t kq = 2 * ((size_t)p.digitsG - 1);
+    if (g3) return {lmk ? (size_t)12288 : (size_t)24576, 6144};
+    return {lmk ? 2 * kq * 2048 : 2 * kq * 4096, kq * 2048};
+}
+void keygen_repack_device(const Params& p, bool g3, bool narrow, const void* d_bsk, uint32_t* d_bsk2, void* stream);
 // LWEEncryptionScheme::Encrypt / Decrypt (lwe-pke.cpp:103-128, 181-226) with plaintext modulus
 // ptmod and ciphertext modulus mod (0: q); len: the dimension (0: n; N with skN for EncryptN's LARGE_DIM)
 void encrypt(const Params& p, const uint64_t* sk, const int* bits, size_t count, uint64_t seed, uint64_t* a,

@@ -157,10 +157,25 @@ int fhe_hip_copy_keys(fhe_hip_ctx* dst, const fhe_hip_ctx* src);
 /* BTKeyGen on the context's device (BinFHEContext::BTKeyGen binfhecontext.cpp:185-200 -> KeyGenAcc
  * rgsw-acc-cggi.cpp:39-96 / rgsw-acc-dm.cpp:39-114 / rgsw-acc-lmkcdey.cpp:39-226, KeySwitchGen
  * lwe-pke.cpp:264-344): generates and loads the keys for sk[n] (mod qKS); bit-identical to
- * fhe_hip_keygen(..., seed, ...) for the sk it returns.  bsk / kskA / kskB (raw layouts, may be
- * NULL) receive a host copy. */
+ * fhe_hip_keygen(..., seed, ...) for the sk it returns.  Every parameter set, the large-precision family and
+ * its timeOptimization map included, is generated on the device straight into the resident layouts: no key is
+ * built on the host.  bsk / kskA / kskB (raw layouts, may be NULL) receive a host copy (with
+ * timeOptimization the three keys concatenated, the sizes fhe_hip_load_bsk / fhe_hip_load_ksk expect).  On
+ * failure the context holds no keys. */
 int fhe_hip_btkeygen_device(fhe_hip_ctx* ctx, const uint64_t* sk, size_t n, uint64_t seed, uint64_t* bsk,
                             uint64_t* kskA, uint64_t* kskB);
+/* What fhe_hip_btkeygen_device does for a set (host only, no device needed), from the descriptor builder the
+ * device generator itself uses: on_device 1 when the set is generated on the device (every supported set);
+ * keys 1, or 3 with timeOptimization; row_pairs the RGSW row pairs drawn over all keys (bsk_words / 2N, less
+ * AP's never-drawn j = 0 slots); ntt_polys the polynomials handed to the batched NTT (2 per row pair);
+ * ksk_rows = N baseKS digitsKS keys; scratch_bytes the peak device memory of the generator's temporaries
+ * (descriptors, secrets, one chunk of row pairs capped at 768 MiB, the switching key's vectors; the export
+ * buffer of a requested raw bsk and the NTT plan's tables are not counted). */
+typedef struct {
+    uint32_t on_device, keys;
+    uint64_t row_pairs, ntt_polys, ksk_rows, scratch_bytes;
+} fhe_hip_keygen_plan;
+int fhe_hip_keygen_plan_get(int paramset, int method, fhe_hip_keygen_plan* out);
 /* ---- the reference's packed transfer format (src/binfhe/include/backend/packed.h:29-307) ----
  * LWE batches byte-compatible with PackLWEBatch / UnpackLWEBatch (backend/packed.cpp:144-279):
  * 64-byte header ("LUXF", type LWE_BATCH = 2), u64 coefficients, sequential or INTERLEAVED (flag 1).
